@@ -14,7 +14,15 @@ time. The K steps are also bracketed by a barrier + torch.cuda.synchronize() on 
 wall time around them is reported as `wall_ms_per_step` (it adds the host's sync and, under
 torchrun, barrier latency, which at C2's ~0.03 ms per step would dominate a 20-step span).
 
-The same JSON line carries, under "workloads", the other BASELINE configs:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only that: it sets the headline
+workload up, warms it up, times its K steps and prints the line. `--dump-outputs DIR` also writes
+what the last timed step left (digests, counters, node records; dump_outputs) as DIR/*.npy.
+Everything below -- the other workloads, the CPU baselines, the full per-workload record -- runs
+only with `--full`.
+
+With `--full` the same JSON line carries, under "workloads", the other BASELINE configs, each over
+at most 20 steps after at most 5 warm-up steps (the defaults) whatever --steps asks of the headline
+(a from-init step of C3 costs a thousand C2 steps):
   c2_init   config 2 as named: ticks [0, 10,000) from init-node (every cluster elects its first
             leader), on `reps` fresh handles.
   c3        config 3: 1,048,576 five-node clusters with 10 % drop, 1 % duplication, delay U[1,50],
@@ -299,7 +307,61 @@ def survey_8d(rate, n, delta):
                     "are skipped exactly, so it exceeds 1): see frac"}
 
 
-def run_workload(name, args, world, rank, local_rank, dist):
+DUMP_DIGESTS = 1 << 20                 # digests written: all clusters up to this many
+DUMP_BLOCKS, DUMP_BLOCK = 64, 256       # node records written: this many runs of clusters
+DUMP_NODE_FIELDS = ("role", "voted_for", "leader_id", "fault", "entries_is_seq", "ls_present",
+                    "votes", "ls_keys", "current_term", "commit_index", "log_len", "deadline",
+                    "last_led_term", "req_count", "res_count", "commit_count")
+
+
+def dump_outputs(sim, directory):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy
+    files under `directory` (every value an integer below 2^53, so exact; 64-bit words as two
+    columns, high and low 32 bits). The simulation is seeded, so two builds given the same
+    arguments must write the same files.
+      digest.npy    [clusters, 2]  the per-cluster state digest (SIM_SPEC §6)
+      counters.npy  [31]           node_ticks, the counters in raftsim.COUNTER_NAMES order,
+                                   payload_max, first_violation_tick (-1: none)
+      nodes.npy     [nodes, 18]    DUMP_NODE_FIELDS and the trace hash of every node of the
+                                   clusters listed in node_clusters.npy, node-major per cluster
+      node_clusters.npy [k]        those clusters' local ids
+    Past DUMP_DIGESTS clusters the digests, and past DUMP_BLOCKS * DUMP_BLOCK clusters the node
+    records, are a fixed sample (generator seeded with 0): under 40 MB in all at any size."""
+    import numpy as np
+    from raftsim import COUNTER_NAMES, _abi
+
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+
+    def halves(u):
+        return np.stack([(u >> np.uint64(32)).astype(np.float64),
+                         (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+    rng = np.random.default_rng(0)
+    dg = sim.digest()
+    if sim.C > DUMP_DIGESTS:
+        dg = dg[np.sort(rng.choice(sim.C, DUMP_DIGESTS, replace=False))]
+    np.save(d / "digest.npy", halves(dg))
+    c = sim.counters()
+    keys = ["node_ticks", *COUNTER_NAMES, "payload_max", "first_violation_tick"]
+    np.save(d / "counters.npy", np.array([-1.0 if c[k] is None else float(c[k]) for k in keys]))
+    blocks = sim.C // DUMP_BLOCK
+    if blocks <= DUMP_BLOCKS:
+        runs = [(0, sim.C)]
+    else:
+        runs = [(int(b) * DUMP_BLOCK, DUMP_BLOCK)
+                for b in np.sort(rng.choice(blocks, DUMP_BLOCKS, replace=False))]
+    rows = []
+    for c0, nc in runs:
+        raw = np.frombuffer(sim.read_nodes_raw(c0, nc), dtype=np.dtype(_abi.Node))
+        cols = [raw[f].astype(np.float64)[:, None] for f in DUMP_NODE_FIELDS]
+        rows.append(np.concatenate(cols + [halves(raw["trace_hash"])], axis=1))
+    np.save(d / "nodes.npy", np.concatenate(rows))
+    np.save(d / "node_clusters.npy",
+            np.concatenate([np.arange(c0, c0 + nc, dtype=np.float64) for c0, nc in runs]))
+
+
+def run_workload(name, args, world, rank, local_rank, dist, dump=None):
     import raftsim
     from raftsim import dist as rdist
 
@@ -330,7 +392,8 @@ def run_workload(name, args, world, rank, local_rank, dist):
     kind = spec["window"]
     extra = {}
     if kind == "violation":
-        return run_violation(name, spec, args, world, rank, dist, make, count, total, offset)
+        return run_violation(name, spec, args, world, rank, dist, make, count, total, offset,
+                             dump)
     if kind == "init" and args.warmup:       # same shape, thrown away: the window starts at init
         w = make()
         for _ in range(args.warmup):
@@ -460,14 +523,16 @@ def run_workload(name, args, world, rank, local_rank, dist):
     if delta["payload_evicted"]:
         # SIM_SPEC §4 P3: an evicted payload entry is the simulator's one fidelity limit
         rec["fidelity_warning"] = "payload entries were evicted from a sender's arena"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(spec, args)
+    if dump and rank == 0:
+        dump_outputs(sims[-1], dump)
     for s in sims:
         s.close()
     return rec
 
 
-def run_violation(name, spec, args, world, rank, dist, make, count, total, offset):
+def run_violation(name, spec, args, world, rank, dist, make, count, total, offset, dump=None):
     """BASELINE config 5: step every rank's clusters chunk by chunk until a violation is counted
     anywhere in the job (MIN all-reduce of the first-violation tick per chunk over RCCL)."""
     from raftsim import dist as rdist
@@ -507,7 +572,7 @@ def run_violation(name, spec, args, world, rank, dist, make, count, total, offse
         "counters": {k: v for k, v in c.items() if v},
     }
     rec["roofline"]["survey_8d"] = survey_8d(rec["value"], n, c)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         import helpers
 
         ref = helpers.oracle(n_clusters=count, cluster_offset=offset, **cfg)
@@ -525,11 +590,13 @@ def run_violation(name, spec, args, world, rank, dist, make, count, total, offse
                       f"{spec['chunk']}-tick chunks, oracle/raftref.c with idle-tick skipping, "
                       f"{threads} threads, {dt:.2f} s",
             "host_cpus": host_cpus()}
+    if dump and rank == 0:
+        dump_outputs(sim, dump)
     sim.close()
     return rec
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -540,7 +607,40 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--full-json", default=None,
                     help="where the full per-workload records go (default gpurun_out/bench_full.json)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every workload after the headline, the CPU baselines and the "
+                         "full per-workload record; without it only the headline workload is "
+                         "set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline workload's final digests, "
+                         "counters and node records to DIR/*.npy (dump_outputs)")
+    return ap.parse_args(argv)
+
+
+EXTRA_STEPS, EXTRA_WARMUP = 20, 5     # the most a workload after the headline runs (the defaults)
+
+
+def plan(args):
+    """(workload names to run, whether the C oracle's CPU baselines run, whether the full record is
+    written). A plain run is the headline alone: set up, warm up, time --steps steps, one line."""
+    names = args.workload.split("+")
+    if not args.full:
+        return names[:1], False, args.full_json is not None
+    return names, not args.no_cpu_baseline, True
+
+
+def extra_args(args):
+    """The arguments the workloads after the headline run under: --steps and --warmup are the
+    headline's, the others keep at most the window their lines were always measured over, however
+    long the headline is asked to run."""
+    extra = argparse.Namespace(**vars(args))
+    extra.steps, extra.warmup = min(args.steps, EXTRA_STEPS), min(args.warmup, EXTRA_WARMUP)
+    return extra
+
+
+def main():
+    args = parse_args()
+    names, args.cpu_baseline, want_full = plan(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -553,21 +653,30 @@ def main():
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl")                           # RCCL on ROCm
 
-    names = args.workload.split("+")
-    recs = {name: run_workload(name, args, world, rank, local_rank, dist) for name in names}
+    extra = extra_args(args)
+    recs = {name: run_workload(name, args if name == names[0] else extra, world, rank, local_rank,
+                               dist, args.dump_outputs if name == names[0] else None)
+            for name in names}
     if rank == 0:
         full = args.full_json or str(ROOT / "gpurun_out" / "bench_full.json")
-        try:
-            Path(full).parent.mkdir(parents=True, exist_ok=True)
-            Path(full).write_text(json.dumps({"n_gpus": world, "steps": args.steps,
-                                              "warmup": args.warmup, "workloads": recs},
-                                             indent=1) + "\n")
-        except OSError as e:                      # the full record is a convenience; the line is not
-            print(f"bench: could not write {full}: {e}", file=sys.stderr)
-            full = None
+        full = write_full(full, world, args, recs) if want_full else None
         print(json.dumps(compact_line(names, recs, world, args, full)), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def write_full(path, world, args, recs):
+    """The full per-workload records as JSON at `path`; returns it, or None if it cannot be
+    written (the full record is a convenience; the line is not)."""
+    try:
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
+        Path(path).write_text(json.dumps({"n_gpus": world, "steps": args.steps,
+                                          "warmup": args.warmup, "workloads": recs},
+                                         indent=1) + "\n")
+    except OSError as e:
+        print(f"bench: could not write {path}: {e}", file=sys.stderr)
+        return None
+    return path
 
 
 def _r(x, d=4):

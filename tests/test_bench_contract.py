@@ -67,6 +67,81 @@ def test_default_warmup_is_the_drivers(bench):
     assert 'ap.add_argument("--steps", type=int, default=20)' in src
 
 
+def test_plain_run_is_the_headline_alone_and_full_is_everything(bench):
+    """Without --full only the headline workload runs, with no CPU baseline and no full record
+    (unless --full-json names one); --full runs every named workload with the CPU baselines, as
+    the benchmark did before the option existed. --dump-outputs takes a directory."""
+    names, cpu, full = bench.plan(bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"]))
+    assert (names, cpu, full) == (["c2"], False, False)
+    a = bench.parse_args(["--workload", "c3+c2", "--full-json", "x.json", "--dump-outputs", "d"])
+    assert bench.plan(a) == (["c3"], False, True) and a.dump_outputs == "d" and not a.full
+    a = bench.parse_args(["--full"])
+    names, cpu, full = bench.plan(a)
+    assert names == a.workload.split("+") and len(names) == 8 and cpu and full
+    assert a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    assert bench.plan(bench.parse_args(["--full", "--no-cpu-baseline"]))[1] is False
+
+
+def test_full_run_bounds_the_other_workloads_windows(bench):
+    """--steps and --warmup size the headline's window; the workloads after it run at most the
+    default 20 steps after 5 warm-up steps, so a --full run with a long headline window costs
+    the headline's extra steps only (a from-init C3 step is ~1000 C2 steps)."""
+    a = bench.parse_args(["--full", "--steps", "100000", "--warmup", "50"])
+    e = bench.extra_args(a)
+    assert (e.steps, e.warmup) == (20, 5) and (a.steps, a.warmup) == (100000, 50)
+    assert bench.window_id(bench.WORKLOADS["c3"], e) == {"kind": "init", "steps": 20}
+    e = bench.extra_args(bench.parse_args(["--full", "--steps", "2", "--warmup", "1"]))
+    assert (e.steps, e.warmup, e.full) == (2, 1, True)
+    e = bench.extra_args(bench.parse_args(["--full"]))
+    assert (e.steps, e.warmup) == (20, 5)
+
+
+def test_dump_outputs_is_exact_float64_and_a_fixed_sample(bench, tmp_path):
+    """dump_outputs on the C oracle's handle (the same ABI): 64-bit words survive as two float64
+    columns, small handles are written whole, and past the thresholds the digests and node records
+    are the same seeded sample on every call."""
+    import numpy as np
+
+    import helpers
+
+    r = helpers.oracle(n_clusters=300, nodes=3, seed=9, hb=300, el_base=500, el_span=500)
+    r.step(3000)
+    bench.dump_outputs(r, tmp_path / "a")
+    f = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert all(v.dtype == np.float64 for v in f.values())
+    dg = f["digest.npy"].astype(np.uint64)
+    assert np.array_equal((dg[:, 0] << np.uint64(32)) | dg[:, 1], r.digest())
+    assert f["counters.npy"][0] == 300 * 3 * 3000 and f["counters.npy"].shape == (31,)
+    assert f["node_clusters.npy"].tolist() == list(range(300))
+    nodes = r.read_nodes()
+    th = f["nodes.npy"][:, -2:].astype(np.uint64)
+    assert ((th[:, 0] << np.uint64(32)) | th[:, 1]).tolist() == [n["trace_hash"] for n in nodes]
+    for j, name in enumerate(bench.DUMP_NODE_FIELDS):
+        assert f["nodes.npy"][:, j].tolist() == [float(n[name]) for n in nodes], name
+    # past the thresholds: a sorted sample, identical from call to call
+    monkey = dict(DUMP_DIGESTS=100, DUMP_BLOCKS=3, DUMP_BLOCK=16)
+    old = {k: getattr(bench, k) for k in monkey}
+    try:
+        for k, v in monkey.items():
+            setattr(bench, k, v)
+        bench.dump_outputs(r, tmp_path / "b")
+        bench.dump_outputs(r, tmp_path / "c")
+    finally:
+        for k, v in old.items():
+            setattr(bench, k, v)
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    for name, arr in b.items():
+        assert np.array_equal(arr, np.load(tmp_path / "c" / name)), name
+    assert b["digest.npy"].shape == (100, 2)
+    ids = b["node_clusters.npy"].astype(int)
+    assert len(ids) == 48 and (np.diff(ids) > 0).all() and (ids[::16] % 16 == 0).all()
+    want = f["nodes.npy"].reshape(300, 3, -1)[ids].reshape(48 * 3, -1)
+    assert np.array_equal(b["nodes.npy"], want)
+    full = (dg[:, 0] << np.uint64(32)) | dg[:, 1]
+    sub = b["digest.npy"].astype(np.uint64)
+    assert set(((sub[:, 0] << np.uint64(32)) | sub[:, 1]).tolist()) <= set(full.tolist())
+
+
 def test_survey_8d_accounting(bench):
     d = {"node_ticks": 10 ** 9, "delivered": 0, "entries_appended": 0}
     r = bench.survey_8d(1e14, 5, d)

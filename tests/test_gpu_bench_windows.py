@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import helpers
+from raftsim import COUNTER_NAMES as BENCH_COUNTERS
 from raftsim import dist as rdist
 
 pytestmark = pytest.mark.gpu
@@ -135,16 +136,17 @@ def test_gpu_c5_time_to_violation_bit_exact():
 
 
 def test_gpu_bench_line_is_one_parseable_line(tmp_path):
-    """bench.py run as the driver runs it (a child process, C2 headline plus one more workload):
-    stdout ends with ONE JSON line well under the ~8,000 characters the driver keeps, carrying the
-    headline keys, roofline and cpu_baseline; the full records land in --full-json."""
+    """bench.py --full run as a child process (C2 headline plus one more workload): stdout ends
+    with ONE JSON line well under the ~8,000 characters the driver keeps, carrying the headline
+    keys, roofline and cpu_baseline; the full records land in --full-json."""
     import json
     import subprocess
     import sys
 
     full = tmp_path / "full.json"
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1",
-                          "--workload", "c2+c4_n9", "--clusters", "4096", "--full-json", str(full)],
+                          "--workload", "c2+c4_n9", "--clusters", "4096", "--full-json", str(full),
+                          "--full"],
                          capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -156,3 +158,52 @@ def test_gpu_bench_line_is_one_parseable_line(tmp_path):
     assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["value"] > 0
     assert rec["roofline"]["avg_launch_ms"] > 0 and rec["cpu_baseline"]["value"] > 0
     assert set(json.loads(full.read_text())["workloads"]) == {"c2", "c4_n9"}
+
+
+def test_gpu_plain_bench_run_times_the_headline_alone_and_dumps_it(tmp_path):
+    """bench.py without --full, as it is run for every change: the headline workload alone (no
+    other workload, no CPU baseline, no full record), --steps timed steps, and the line's headline
+    keys. --dump-outputs writes what the last timed step left as float64 .npy files: the digests
+    and counters equal the C oracle's after the same warm-up + timed ticks (so they are the same
+    from run to run), the node records are the sampled clusters' read_nodes fields."""
+    import json
+    import subprocess
+    import sys
+
+    clusters, steps, warmup = 4096, 3, 1
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps",
+                          str(steps), "--warmup", str(warmup), "--clusters", str(clusters),
+                          "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+    assert rec["metric"] == "simulated node-ticks/sec (5-node Raft)"
+    assert rec["unit"] == "node-ticks/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "u32" and rec["steps"] == steps and rec["warmup"] == warmup
+    assert rec["ms_per_step"] > 0
+    # value = the timed steps' node-ticks over their device time: --steps sets the timed steps
+    assert rec["value"] == pytest.approx(clusters * 5 * TICKS / (rec["ms_per_step"] * 1e-3),
+                                         rel=1e-4)
+    assert "workloads" not in rec and "cpu_baseline" not in rec and rec["full_record"] is None
+    assert not list(tmp_path.glob("*.json"))
+
+    spec = BENCH.WORKLOADS["c2"]
+    r = _oracle(n_clusters=clusters, **spec["cfg"])
+    r.step((warmup + steps) * TICKS)
+    files = {f.name: np.load(f) for f in dump.iterdir()}
+    assert set(files) == {"digest.npy", "counters.npy", "nodes.npy", "node_clusters.npy"}
+    assert all(a.dtype == np.float64 for a in files.values())
+    dg = files["digest.npy"].astype(np.uint64)
+    assert np.array_equal((dg[:, 0] << np.uint64(32)) | dg[:, 1], r.digest())
+    c = r.counters()
+    keys = ["node_ticks", *BENCH_COUNTERS, "payload_max", "first_violation_tick"]
+    assert files["counters.npy"].tolist() == [-1.0 if c[k] is None else float(c[k]) for k in keys]
+    ids = files["node_clusters.npy"].astype(int)
+    assert ids.tolist() == list(range(clusters))           # below the sampling threshold: all
+    nodes = r.read_nodes()
+    assert files["nodes.npy"].shape == (clusters * 5, len(BENCH.DUMP_NODE_FIELDS) + 2)
+    for row in (0, 7, clusters * 5 - 1):
+        want = [float(nodes[row][f]) for f in BENCH.DUMP_NODE_FIELDS]
+        want += [float(nodes[row]["trace_hash"] >> 32), float(nodes[row]["trace_hash"] & 0xFFFFFFFF)]
+        assert files["nodes.npy"][row].tolist() == want
