@@ -109,6 +109,82 @@ def cpu_threads():
     return max(1, n)
 
 
+BURST_GATE = 2 ** 28 - 1      # the burst engine runs in launches that end at or before this tick
+
+
+def burst_leader(nodes, t):
+    """The burst engine's entry condition (tick_wave.hpp BURST, the `lok`/`bok` test) on one
+    cluster's read_nodes() records at tick `t`: exactly one live leader, holding at most one
+    request and no response; every other live node a non-leader that names it as :leader-id, with
+    empty queues and a deadline ahead. Halted nodes are ignored. Returns the leader's index in
+    `nodes` (0-based), or None where the condition does not hold."""
+    live = [(k, n) for k, n in enumerate(nodes) if n["fault"] == 0]
+    leaders = [(k, n) for k, n in live if n["role"] == 2]
+    if len(leaders) != 1:
+        return None
+    lk, ln = leaders[0]
+    if ln["req_count"] > 1 or ln["res_count"] != 0:
+        return None
+    for k, n in live:
+        if k != lk and (n["leader_id"] != lk + 1 or n["req_count"] or n["res_count"]
+                        or n["deadline"] <= t):
+            return None
+    return lk
+
+
+def burst_eligible(nodes, t):
+    """True when the burst engine's entry condition (burst_leader) holds."""
+    return burst_leader(nodes, t) is not None
+
+
+def burst_witness(cfg, ticks=20000, stride=7, clusters=16, tick0=0, setup=None):
+    """Run the first `clusters` clusters of `cfg` on the oracle (D13: the same clusters as in the
+    full case), `stride` ticks at a time from `tick0` (after `setup(handle)`, if given), and count
+    how often the states the burst engine handles occur, sampled after each step at t = the
+    handle's tick:
+      eligible  samples where burst_eligible holds (eligible_below / eligible_above: split at
+                t < BURST_GATE and at or above it);
+      entered   false -> true transitions per cluster; broke: true -> false transitions;
+      longer    eligible samples where a live non-leader's log is longer than the leader's;
+      halted    eligible samples with at least one halted node;
+      samples   all samples taken.
+    Returns (counts, counters())."""
+    N = cfg["nodes"]
+    h = oracle(**dict(cfg, n_clusters=clusters))
+    oracle_threads(h, min(cpu_threads(), clusters))
+    if tick0:
+        h.set_tick(tick0)
+    if setup is not None:
+        setup(h)
+    w = dict(eligible=0, eligible_below=0, eligible_above=0, entered=0, broke=0, longer=0,
+             halted=0, samples=0)
+    was = [False] * clusters
+    done = 0
+    while done < ticks:
+        n = min(stride, ticks - done)
+        h.step(n)
+        done += n
+        t = h.tick
+        recs = h.read_nodes(0, clusters)
+        for c in range(clusters):
+            nodes = recs[c * N:(c + 1) * N]
+            lk = burst_leader(nodes, t)
+            ok = lk is not None
+            w["samples"] += 1
+            if ok:
+                w["eligible"] += 1
+                w["eligible_below" if t < BURST_GATE else "eligible_above"] += 1
+                w["longer"] += any(m["fault"] == 0 and k != lk and m["log_len"] > nodes[lk]["log_len"]
+                                   for k, m in enumerate(nodes))
+                w["halted"] += any(m["fault"] != 0 for m in nodes)
+            w["entered"] += ok and not was[c]
+            w["broke"] += was[c] and not ok
+            was[c] = ok
+    counters = h.counters()
+    h.close()
+    return w, counters
+
+
 def describe_cluster_diff(a, b, cluster):
     """Human-readable differences between cluster `cluster` of two backends."""
     lines = []

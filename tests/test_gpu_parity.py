@@ -17,6 +17,13 @@ FAULTS = dict(drop_ppm=100000, dup_ppm=10000, dmin=1, dmax=50, part_ppm=100000)
 BURSTS = dict(client_period=16384, client_burst=2048, client_redirects=4)
 C4_BURSTS = dict(log_cap=4096, client_ppm=500000, client_period=8192, client_burst=2048,
                  client_redirects=4)
+# the burst-engine fault cases: short timers and delays with drops, partitions and duplicates
+# (medium client rate), and config-4-rate bursts under fast timers
+MID = dict(hb=100, el_base=150, el_span=150, dmin=1, dmax=8, drop_ppm=100000, part_ppm=100000,
+           dup_ppm=10000)
+FAST = dict(hb=300, el_base=500, el_span=500)
+B4 = dict(log_cap=4096, client_ppm=500000, client_period=4096, client_burst=1024,
+          client_redirects=4)
 
 CASES = {
     # C2 shape (no faults, no client traffic), smaller cluster count
@@ -86,6 +93,27 @@ CASES = {
     "burst_launches_n8": dict(n_clusters=512, nodes=8, seed=95, client_ppm=500000,
                               client_period=1024, client_burst=256, client_redirects=4,
                               ticks_per_launch=37, log_cap=1500),
+    # the burst engine under faults (tests/test_burst_witness.py shows on the oracle that these
+    # reach its states). Medium client rate, short timers, drops, partitions, duplicates: heartbeats,
+    # fault-caused elections and faulty messages fall between injections, so the engine is entered
+    # after an election and left for a lost heartbeat, with halted nodes and with followers whose
+    # logs are longer than the new leader's (the `pre = own[as]` compare path); n9 fills its logs
+    # (OVERFLOW at log_cap), n8 is the vote-without-log-check variant
+    "burst_faults_mid_n7": dict(n_clusters=256, nodes=7, seed=121, log_cap=1024, client_ppm=30000,
+                                client_redirects=4, **MID),
+    "burst_faults_mid_n9": dict(n_clusters=256, nodes=9, seed=123, log_cap=1024, client_ppm=60000,
+                                client_redirects=2, **MID),
+    "burst_variant_mid_n8": dict(n_clusters=256, nodes=8, seed=125, log_cap=1024, client_ppm=30000,
+                                 client_redirects=4, variant_flags=1, **MID),
+    # ... with an odd arena a little above 2L and no trace rings: the engine's arena wrap and its
+    # read-ahead of the follower's next entry run across the arena's end
+    "burst_arena_odd_n7": dict(n_clusters=256, nodes=7, seed=127, log_cap=48, arena_cap=101,
+                               client_ppm=30000, client_redirects=4, **MID),
+    # C4-rate bursts with faults: messages in flight when a burst starts and when it ends; with
+    # two-slot inboxes on top
+    "burst_faults_c4_n9": dict(n_clusters=256, nodes=9, seed=103, **B4, **FAST, **FAULTS),
+    "burst_faults_n8_inbox2": dict(n_clusters=256, nodes=8, seed=111, inbox_cap=2, **B4, **FAST,
+                                   **FAULTS),
     # config 3 / 5 shapes with the bursty, redirect-following client
     "c3_bursts": dict(n_clusters=2048, nodes=5, seed=1, client_ppm=80000, log_cap=256,
                       **BURSTS, **FAULTS),
@@ -454,7 +482,10 @@ def test_gpu_tick_horizon():
     dict(n_clusters=2048, nodes=7, seed=3, client_ppm=20000, log_cap=128, **FAULTS),
     dict(n_clusters=1024, nodes=5, seed=41, client_ppm=2000, log_cap=256, variant_flags=2,
          commit_stream_cap=64, **FAULTS),
-], ids=["c2_shape", "faults_n7", "spec"])
+    # N >= 7 with client traffic: the burst engine's ticks feed the packing key (tick_wave.hpp)
+    CASES["burst_faults_mid_n7"],
+    CASES["burst_faults_c4_n9"],
+], ids=["c2_shape", "faults_n7", "spec", "burst_faults_mid_n7", "burst_faults_c4_n9"])
 def test_gpu_schedule_invariance(cfg):
     """RAFT_SCHED_ALIGNED (clusters regrouped onto waves by next event before every launch) and
     RAFT_SCHED_FIXED produce the same per-cluster digests and counters, launch by launch."""
