@@ -21,6 +21,34 @@
 
 #include "../../include/raftsim.h"
 
+// Every compile-time switch of the kernels, with its default. The product is built with none of
+// them set: without RS_DIAG_BUILD, defining one is an error. A RS_DIAG_BUILD library
+// (scripts/build_variants.sh) carries the tag "diag" instead of a source hash (raftsim.hip), which
+// raftsim.check_build refuses: it is only ever loaded on purpose, through RAFTSIM_LIB.
+#if defined(RS_BURST) && !defined(RS_DIAG_BUILD)
+#error "RS_BURST is a diagnostic switch: it needs -DRS_DIAG_BUILD"
+#elif !defined(RS_BURST)        // 0: no burst engine (tick_wave.hpp); same results
+#define RS_BURST 1
+#endif
+#if defined(RS_BURST_MIN) && !defined(RS_DIAG_BUILD)
+#error "RS_BURST_MIN is a diagnostic switch: it needs -DRS_DIAG_BUILD"
+#elif !defined(RS_BURST_MIN)    // the shortest engine run worth an entry (ticks); same results
+#define RS_BURST_MIN 16
+#endif
+#if defined(RS_BURST_SKIP) && !defined(RS_DIAG_BUILD)
+#error "RS_BURST_SKIP is a diagnostic switch: it needs -DRS_DIAG_BUILD"
+#elif !defined(RS_BURST_SKIP)   // trips a wave skips the engine's entry check after a miss; same results
+#define RS_BURST_SKIP 8
+#endif
+#if defined(RS_BURST_DIAG) && !defined(RS_DIAG_BUILD)
+#error "RS_BURST_DIAG is a diagnostic switch: it needs -DRS_DIAG_BUILD"
+#elif !defined(RS_BURST_DIAG)   // 1: engine ticks, entries, yields and trips in four counters C4
+#define RS_BURST_DIAG 0         // never uses (WRONG counters; scripts/burst_diag.py)
+#endif
+#if defined(RS_WAVELOG) && !defined(RS_DIAG_BUILD)   // defined: per-wave timelines, phase stamps
+#error "RS_WAVELOG is a diagnostic switch: it needs -DRS_DIAG_BUILD"
+#endif
+
 namespace rs {
 
 constexpr uint32_t INF = 0xFFFFFFFFu;
@@ -392,11 +420,8 @@ __device__ __forceinline__ uint2* arena_of(const DevSim& S, uint32_t gi) {
   return reinterpret_cast<uint2*>(S.arena) + (size_t)gi * S.A;
 }
 
-#ifndef RS_KO_CTR
-#define RS_KO_CTR 0     // knock-out switch of timing-only diagnostic builds: never set in the product
-#endif
 __device__ __forceinline__ void lctr_add(uint32_t* lctr, int i, uint32_t v) {
-  if (!RS_KO_CTR && v) atomicAdd(&lctr[i], v);
+  if (v) atomicAdd(&lctr[i], v);
 }
 
 // Stable insert of message (m0 = arrival,hdr,term,a ; m1 = b,eterm,eval,poff) into the node's own

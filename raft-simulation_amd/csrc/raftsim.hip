@@ -37,7 +37,6 @@ static int fail(int code, const char* fmt, const char* detail = "") {
                                       hipGetErrorString(e_));                      \
   } while (0)
 
-
 struct Shard {
   raft_sim_config_t cfg;
   uint32_t N, Q, L, A, C, NN, tpl;
@@ -103,6 +102,8 @@ constexpr uint32_t RESORT_EVERY = 2;
 // LITE handles: a steady-state packing is a rotation of itself one launch later (every cluster's
 // next event moves by the same launch length), so it is rebuilt every 8th launch
 constexpr uint32_t RESORT_EVERY_LITE = 8;
+// clusters per handle from which storm ticks run the storm kernel (raft_sim_create has the numbers)
+constexpr uint32_t STORM_MIN_CLUSTERS = 131072;
 
 // Exported functions take their C linkage from the declarations in include/raftsim.h.
 
@@ -260,8 +261,10 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
   // C4's 16,384 clusters its 256 waves ran 36 ms against the lane-per-node body's 14): below that
   // the storm ticks run the general STORM body.
   // (Its registers hold arrivals below 2^28 and hop counts below 16.)
-  uint32_t storm_min = 131072;
+  uint32_t storm_min = STORM_MIN_CLUSTERS;
+#ifdef RS_DIAG_BUILD   // scripts/storm_probe.py forces either path; the product takes no override
   if (const char* sm = getenv("RAFTSIM_STORM_MIN_CLUSTERS")) storm_min = (uint32_t)strtoul(sm, nullptr, 10);
+#endif
   if (s->storm_until && s->C >= storm_min && cfg->el_base < (1u << 28) && cfg->client_redirects < 16 &&
       ((rc = dalloc(s, &s->d.storm_list, s->C)) ||
                          (rc = dalloc(s, &s->d.storm_count, 1)))) {
@@ -1065,7 +1068,12 @@ int raft_sim_read_counters(raft_sim_t* r, raft_counters_t* out) {
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was
 // compiled from (raftsim/_build.py; __graft_entry__.build_lib passes it), also findable in the
-// file's bytes as "RAFTSIM_SRC_HASH=<hash>" without loading it.
+// file's bytes as "RAFTSIM_SRC_HASH=<hash>" without loading it. A diagnostic build (device.hpp's
+// switches) is "diag" whatever hash was passed: raftsim.check_build refuses it.
+#ifdef RS_DIAG_BUILD
+#undef RAFTSIM_SRC_HASH
+#define RAFTSIM_SRC_HASH "diag"
+#endif
 #ifndef RAFTSIM_SRC_HASH
 #define RAFTSIM_SRC_HASH "unknown"
 #endif

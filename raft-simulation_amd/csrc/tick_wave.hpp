@@ -12,54 +12,6 @@
 
 namespace rs {
 
-#ifndef RS_PROV
-#define RS_PROV 1
-#endif
-#ifndef RS_PROV_SEARCH
-#define RS_PROV_SEARCH 1
-#endif
-#ifndef RS_PROV_MIN_N
-#define RS_PROV_MIN_N 6
-#endif
-#ifndef RS_RC_MIN_N
-#define RS_RC_MIN_N 6
-#endif
-#ifndef RS_REGS_MIN_N
-#define RS_REGS_MIN_N 6
-#endif
-#ifndef RS_KA_HOIST
-#define RS_KA_HOIST 1
-#endif
-#ifndef RS_SHFL_GUARD
-#define RS_SHFL_GUARD 1
-#endif
-#ifndef RS_BURST
-#define RS_BURST 1
-#endif
-#ifndef RS_BURST_KO_CMP  // timing-only knock-out of the burst engine's log-matching loads (wrong results)
-#define RS_BURST_KO_CMP 0
-#endif
-#ifndef RS_BURST_MIN      // the shortest engine run worth an entry (ticks)
-#define RS_BURST_MIN 16
-#endif
-#ifndef RS_BURST_SKIP     // trips a wave skips the engine's entry check after one that found no entry
-#define RS_BURST_SKIP 8
-#endif
-#ifndef RS_BURST_PRE      // evaluate the engine's entry only on trips with an injection or a queued leader
-#define RS_BURST_PRE 0
-#endif
-#ifndef RS_BURST_DIAG   // timing-only diagnostic builds: engine ticks, entries, yields and trips in
-#define RS_BURST_DIAG 0 // four counters C4 never uses (wrong counters): never set in the product
-#endif
-
-// knock-out switches of timing-only diagnostic builds (wrong results): never set in the product
-#ifndef RS_KO_P4
-#define RS_KO_P4 0
-#endif
-#ifndef RS_KO_LOGM
-#define RS_KO_LOGM 0
-#endif
-
 __device__ __forceinline__ void violation(uint32_t* lctr, int kind, uint32_t t) {
   atomicAdd(&lctr[kind], 1u);
   atomicMin(&lctr[LCTR_FIRSTVIOL], t);
@@ -301,7 +253,7 @@ __device__ __forceinline__ void spec_handle(
       // Payload provenance (tick_wave's PROV): when this node's positions [mb, hi) are unevicted
       // copies of the same sender slots this payload names (key mpoff - mb) and none of the
       // payload is evicted, every term agrees and the search ends at hi.
-      if (RS_PROV_SEARCH && E == 0 && pm && (pm & 15) == src && pk == mpoff - mb && ((pm >> 4) & 0x3FFFu) <= mb &&
+      if (E == 0 && pm && (pm & 15) == src && pk == mpoff - mb && ((pm >> 4) & 0x3FFFu) <= mb &&
           hi <= (pm >> 18))
         kk = hi > mb ? hi : mb;
       if (kk < hi) {
@@ -339,6 +291,10 @@ __device__ __forceinline__ void spec_handle(
       lctr_add(lctr, RAFT_CTR_PAYLOAD_EVICTED, ncmp < E ? ncmp : E);
       const uint32_t mc = mb + pcnt - kk;
       if (mc) {                               // truncate at kk, append payload [kk - b, pcnt)
+        // (n.len may get shorter below without tick_wave's shorten_log, the rule for every other
+        // shortening: mc != 0 makes this a payload append, and P3 rewrites pk and pm for one, so
+        // the stale provenance is never read. A path that shortens a log and appends no payload
+        // must go through shorten_log.)
         pkind = PLAN_PAYLOAD; psrc = src; ppoff = mpoff + (kk - mb); ppcnt = mc;
         pold_base = n.base;
         if (kk < n.len || n.base + n.len != n.front) {
@@ -515,34 +471,38 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
   constexpr uint32_t ALL = ((1u << (N + 1)) - 1) & ~1u;
   constexpr uint32_t MAJ = SPEC ? N / 2 + 1 : (N + 1) / 2;   // majority? (core.clj:19-21) / strict
   // payload provenance for the checker (below): the kernels with long replicated runs
-  constexpr bool PROV = RS_PROV && !LITE && !STORM && (SPEC || N >= RS_PROV_MIN_N);
+  constexpr bool PROV = !LITE && !STORM && (SPEC || N >= 6);
   // RC: the counters a client burst bumps on every trip (client-set events, redirects, deliveries,
   // appended entries, injections, messages to halted nodes) are kept per lane in registers and
   // added to the wave's LDS counters once at the end: N >= 7 (three waves per SIMD anyway; C4
   // -5 %) and Spec-Raft (C3-spec -3 %); the faithful N <= 5 kernel measured the same either way,
   // and the faithful N = 6 kernel keeps its four waves per SIMD without them
-  constexpr bool RC = !LITE && ((N >= RS_RC_MIN_N && N >= 7) || (SPEC && !STORM));
+  constexpr bool RC = !LITE && (N >= 7 || (SPEC && !STORM));
   uint32_t rc_cs = 0, rc_red = 0, rc_del = 0, rc_app = 0, rc_inj = 0, rc_halt = 0;
   uint32_t* const rdel = RC ? &rc_del : nullptr;
   uint32_t* const rhalt = RC ? &rc_halt : nullptr;
   // REGS: the per-cluster trip count (the packing key), the client batch's start and the per-lane
   // deferred-draw bit in registers instead of LDS where registers are to spare (N >= 7, and the
   // Spec-Raft N = 6 kernel): LDS round trips off every trip's chain (C4-N9 -9 %)
-  constexpr bool REGS = !LITE && N >= RS_REGS_MIN_N && (N >= 7 || (SPEC && !STORM));
+  constexpr bool REGS = !LITE && (N >= 7 || (N == 6 && SPEC && !STORM));
   uint32_t trips_r = 0, dpend_r = 0, cb_r = 0;   // cb_r: the client batch's start (cq_base)
   // (REGS kernels also read the kernel-argument fields a trip's common handlers use once, here,
-  // instead of a scalar load and its wait at every use)
-  uint32_t ka_el_base = 0, ka_el_span = 0, ka_hb = 0, ka_L = 0, ka_redir = 0;
+  // instead of a scalar load and its wait at every use; for the others the hoist cost C3 a wave
+  // per SIMD, so they read them at the use: KA below is the one place that chooses)
+  uint32_t ka_el_base = 0, ka_el_span = 0, ka_hb = 0, ka_L = 0, ka_client_redirects = 0;
   bool ka_fixd = false;
-  if constexpr (REGS && RS_KA_HOIST) {
+  if constexpr (REGS) {
     KDevSim* const K0 = kargs();
     ka_el_base = K0->el_base; ka_el_span = K0->el_span; ka_hb = K0->hb; ka_L = K0->L;
-    ka_redir = K0->client_redirects; ka_fixd = K0->dmin == K0->dmax;
+    ka_client_redirects = K0->client_redirects; ka_fixd = K0->dmin == K0->dmax;
   }
-  constexpr bool KAH = REGS && RS_KA_HOIST;
+  // (KA_AT: from a kargs pointer the site holds. Macros: a lambda or an inline function here moved
+  // the whole kernel's register allocation. The burst engine, REGS only, names the copies.)
+#define KA_AT(K, f) (REGS ? ka_##f : (K)->f)
+#define KA(f) KA_AT(kargs(), f)
   // BURST: the faithful N >= 7 kernels run a cluster's client burst under a stable leader in a
   // lane loop of its own (the burst engine in the tick loop below)
-  constexpr bool BURST = RS_BURST && KAH && !SPEC && !STORM && !TRACE && !LITE && !CATCH && N >= 7;
+  constexpr bool BURST = RS_BURST && REGS && !SPEC && !STORM && !TRACE && !LITE && !CATCH && N >= 7;
   // the wave's cells, counters, leader rows and per-lane / per-cluster words
   uint32_t* cells = smem;
   uint32_t* lctr = cells + cell_words<N>();
@@ -592,6 +552,14 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
     // entry appends land at to or past it, remove-from! clamps to, a payload append replaces both.
     // The checker then skips a pair whose positions are such copies on both sides (P4).
     uint32_t pk = 0, pm = 0;
+    // PROV is sound only while pm's `to` never exceeds the log: every path that makes n.len
+    // shorter goes through shorten_log (but see spec_handle's truncate-and-append)
+    auto shorten_log = [&](uint32_t len) {
+      n.len = len;
+      if constexpr (PROV) {
+        if ((pm >> 18) > len) pm = (pm & 0x3FFFFu) | len << 18;
+      }
+    };
     uint32_t cnext = INF, ccount = 0;         // client-set injection cursor (cluster-replicated)
     if (active) {
       const uint32_t fl = hp[HF_FLAGS * N], mk = hp[HF_MASKS * N], qm = hp[HF_QMETA * N];
@@ -729,7 +697,6 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
   #define RS_PX(v) do {} while (0)
   #endif
 
-
     // Every cluster keeps its own clock. Ticks before a cluster's next event change nothing for it
     // (every handler, injection and delivery is keyed to a deadline, a queue head or the injection
     // cursor), and clusters never interact, so each trip of the loop runs every cluster's next
@@ -822,12 +789,12 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
       // do: P0's injection (batch, counters, to-halted), P1's handlers (trace hash, re-arm, the
       // deferred draw of a follower, redirect or abandon), P2's delivery to the leader, P3's entry
       // append and P4's log matching of the new entry against every other node's log.
+      // (Evaluating the entry only on trips with an injection or a queued leader -- one more
+      // ballot ahead of the check -- was tried and not kept: bskip is what makes the check cheap.)
       if constexpr (BURST) {
         if (bskip) {
           --bskip;
-        } else if (bclient && (!RS_BURST_PRE ||
-                        __ballot(active && t < tend &&
-                                 (t == cnext || (n.role == RAFT_LEADER && n.rq.c == 1))))) {
+        } else if (bclient) {
           const bool live0 = active && !n.fault;
           const uint32_t lmask = (uint32_t)(__ballot(live0) >> bl0) & cmask;
           const uint32_t ldm = (uint32_t)(__ballot(live0 && n.role == RAFT_LEADER) >> bl0) & cmask;
@@ -881,7 +848,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
               // comparison, loaded a tick ahead of its use)
               uint32_t as = (n.base + Llen0) % A;
               uint2 pre = make_uint2(0, 0);
-              if (!RS_BURST_KO_CMP && !isL && n.len > Llen0) pre = own[as];
+              if (!isL && n.len > Llen0) pre = own[as];
               uint32_t tc = t;
               for (;;) {
                 if (tc >= tend || (tc > tlim && tc != t)) break;
@@ -905,7 +872,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                 if (RS_BURST_DIAG && k0 == 0) lctr_add(lctr, RAFT_CTR_DROPPED, 1);
                 // a live follower's event: redirect-client (server.clj:62-63), or abandon
                 const bool tof = injn && !toL && ((lmask >> (tgt - 1)) & 1);
-                const bool red = tof && ka_redir != 0;
+                const bool red = tof && ka_client_redirects != 0;
                 const uint32_t pv = rc ? qv0 : val;      // the client-set the leader takes
                 // the ring after the tick: the injection behind a queued one, or a redirect
                 // arriving at tc + 1 (P2), else empty
@@ -949,7 +916,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                   if (isL) own[as] = make_uint2(Lterm, pv);
                   const bool conf = !isL && n.len > p && pre.x == Lterm && pre.y != pv;
                   as = as + 1 == A ? 0u : as + 1;
-                  if (!RS_BURST_KO_CMP && !isL && n.len > p + 1) pre = own[as];
+                  if (!isL && n.len > p + 1) pre = own[as];
                   if (p < omax && cluster_any(conf) && isL) violation(lctr, RAFT_CTR_VIOL_LOG, tc);
                 }
                 tc = max(tc + 1, min(min(cnext, rc ? tc + 1 : INF), min(min(Ldl, fmin), tend)));
@@ -1078,10 +1045,10 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                     (!LITE && req_ok && n.role != RAFT_LEADER && n.lid == 0);
       if (have_w || tdraw) {
         RS_PX(wl_px2);
-        w = event_draw(sg, id, tdraw ? n.deadline - (KAH ? ka_el_base : kargs()->el_base) : t, S);
+        w = event_draw(sg, id, tdraw ? n.deadline - KA(el_base) : t, S);
       }
       if (tdraw) {
-        n.deadline += __umulhi(w.y, KAH ? ka_el_span : kargs()->el_span);
+        n.deadline += __umulhi(w.y, KA(el_span));
         if constexpr (REGS) dpend_r = 0;
         else dpend[lane] = 0;
       }
@@ -1229,13 +1196,10 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                 ra = make_uint4(RAFT_MSG_APPEND_RESPONSE | id << 3, n.term, 0, 0);
               } else if (!consistent) {
                 ra = make_uint4(RAFT_MSG_APPEND_RESPONSE | id << 3, n.term, 0, 0);
-                n.len = n.len > mb ? n.len - mb : 0;          // remove-from! 78-81
-                if constexpr (PROV) {
-                  if ((pm >> 18) > n.len) pm = (pm & 0x3FFFFu) | n.len << 18;
-                }
+                shorten_log(n.len > mb ? n.len - mb : 0);     // remove-from! 78-81
                 n.seq = 1;
               } else {
-                if (n.len + pcnt > (KAH ? ka_L : kargs()->L)) {
+                if (n.len + pcnt > KA(L)) {
                   fault = RAFT_FAULT_OVERFLOW;
                   break;
                 }
@@ -1269,7 +1233,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                 emit = 4;
                 break;
               }
-              if (n.len + 1 > (KAH ? ka_L : kargs()->L)) {
+              if (n.len + 1 > KA(L)) {
                 fault = RAFT_FAULT_OVERFLOW;
                 break;
               }
@@ -1347,7 +1311,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
           // (D4); Spec-Raft keeps Raft's timers (SIM_SPEC §8)
           if (n.role == RAFT_LEADER) {
             if (!SPEC || ev == 7 || elected) {
-              n.deadline = t + (KAH ? ka_hb : kargs()->hb);
+              n.deadline = t + KA(hb);
               if constexpr (REGS) dpend_r = 0;
               else dpend[lane] = 0;
             }
@@ -1356,8 +1320,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
             if (SPEC && !have_w) w = event_draw(sg, id, t, S);
             const bool defer = !SPEC && !have_w;
             KDevSim* const K = kargs();
-            n.deadline = t + (KAH ? ka_el_base : K->el_base) +
-                         (defer ? 0u : __umulhi(w.y, KAH ? ka_el_span : K->el_span));
+            n.deadline = t + KA_AT(K, el_base) + (defer ? 0u : __umulhi(w.y, KA_AT(K, el_span)));
             if (!SPEC) {                                       // the draw is deferred
               if constexpr (REGS) dpend_r = defer;
               else dpend[lane] = defer;
@@ -1401,7 +1364,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
           // (a stepped-down leader keeps its :leader-id) goes through the sender record alone.
           if (!LITE && emit == 4) {
             emit = 0;
-            if (mb >= (KAH ? ka_redir : kargs()->client_redirects)) {
+            if (mb >= KA(client_redirects)) {
               lctr_add(lctr, RAFT_CTR_CLIENT_ABANDONED, 1);
             } else {
               uint32_t dst = n.lid;
@@ -1573,7 +1536,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
       const int appended_at = m ? (int)(n.len - m) : -1;
       if (!STORM && __ballot(m || papplied || (TRACE && tr_cnt))) {
         // (the sender's frontier matters to payload appends only: no shuffle on entry-only trips)
-        const uint32_t sfront = !RS_SHFL_GUARD || __ballot(m && pkind == PLAN_PAYLOAD)
+        const uint32_t sfront = __ballot(m && pkind == PLAN_PAYLOAD)
                                     ? (uint32_t)__shfl(n.front, bl + (int)psrc - 1) : 0u;
         if (m) {
           const uint32_t pold_len = n.len - m;
@@ -1635,7 +1598,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
       // ---------------------------------------------------------------- P4 invariant checker
       // the majority-match scan can raise hwm only when the leader's log reaches past it
       const bool mcheck = (elected || mchg) && n.len > hidx;
-      if (!RS_KO_P4 && !STORM && __ballot(elected || appended_at >= 0 || mcheck)) {
+      if (!STORM && __ballot(elected || appended_at >= 0 || mcheck)) {
         if (__ballot(elected)) {                       // election safety
           bool bad = false;
   #pragma unroll
@@ -1645,7 +1608,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
           }
           if (bad) violation(lctr, RAFT_CTR_VIOL_ELECTION, t);
         }
-        if (!RS_KO_LOGM && __ballot(appended_at >= 0)) {              // log matching
+        if (__ballot(appended_at >= 0)) {                             // log matching
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // peers' P3 arena writes
           // Each lane b compares its own log with the new entries of every other node a of its
           // cluster that appended this tick, pair after pair, W positions per trip of one
@@ -1745,13 +1708,13 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
           // scratch, and their payloads are short)
           KDevSim* const KG = kargs();
           if constexpr (N >= 6) {
-            if (KAH ? ka_fixd : KG->dmin == KG->dmax) log_match(std::true_type{});
+            if (REGS ? ka_fixd : KG->dmin == KG->dmax) log_match(std::true_type{});
             else log_match(std::false_type{});
           } else {
             log_match(std::false_type{});
           }
           uint32_t fa = 0;
-          if (!RS_SHFL_GUARD || __ballot(found != 0)) {       // (a conflict is rare)
+          if (__ballot(found != 0)) {                         // (a conflict is rare)
   #pragma unroll
             for (int s = 0; s < N; ++s) fa |= (uint32_t)__shfl((int)found, bl + s);
           }
@@ -2054,5 +2017,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
     if (v) atomicMax(&ctr[RAFT_CTR_COUNT + 1], (unsigned long long)v);
   }
 }
+#undef KA
+#undef KA_AT
 
 }  // namespace rs

@@ -31,6 +31,10 @@ def check_build():
     if want is None:
         raise RaftSimError("kernel sources missing beside the library: cannot check which sources "
                            f"{LIB_PATH} was built from")
+    if got == "diag":
+        raise RaftSimError(f"{LIB_PATH} is a diagnostic build (RS_DIAG_BUILD: its results or "
+                           "counters may be wrong): load one only through RAFTSIM_LIB, and "
+                           "rebuild the product with __graft_entry__.build_lib(force=True)")
     if got != want:
         raise RaftSimError(f"{LIB_PATH} was built from kernel sources {got}, the tree holds "
                            f"{want}: rebuild with __graft_entry__.build()")

@@ -18,7 +18,8 @@ KERNEL_SOURCES = ["raft-simulation_amd/csrc/tick_kernel.hip",
                   "raft-simulation_amd/csrc/storm_kernel.hip",
                   "raft-simulation_amd/csrc/tick_wave.hpp", "raft-simulation_amd/csrc/device.hpp",
                   "raft-simulation_amd/csrc/raftsim.hip", "include/raftsim.h"]
-_TAG = re.compile(rb"RAFTSIM_SRC_HASH=([0-9a-f]{16}|unknown)")
+# "diag": a diagnostic build (csrc/device.hpp's switches, RS_DIAG_BUILD), whatever its sources
+_TAG = re.compile(rb"RAFTSIM_SRC_HASH=([0-9a-f]{16}|unknown|diag)")
 
 
 def source_hash(root: Path = REPO) -> str | None:
@@ -33,7 +34,8 @@ def source_hash(root: Path = REPO) -> str | None:
 
 
 def embedded_hash(lib: Path) -> str | None:
-    """The source hash a built libraftsim.so carries (None if it carries none)."""
+    """The source hash a built libraftsim.so carries ("diag" for a diagnostic build; None if it
+    carries none)."""
     try:
         m = _TAG.search(Path(lib).read_bytes())
     except OSError:

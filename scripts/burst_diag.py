@@ -1,5 +1,6 @@
-"""Per-launch burst-engine diagnostics of a -DRS_BURST_DIAG=1 build (tick_wave.hpp; wrong counters,
-timing only): engine ticks, engine entries, yields and tick-loop trips per launch.
+"""Per-launch burst-engine diagnostics of a -DRS_BURST_DIAG=1 build (scripts/build_variants.sh, a
+diagnostic build: wrong counters, timing only): engine ticks, engine entries, yields and tick-loop
+trips per launch.
 Usage: python scripts/burst_diag.py LIB c4_n9 [c4_n7 ...]"""
 import sys
 from pathlib import Path

@@ -1,5 +1,6 @@
 """The C ABI: header <-> ctypes layouts, exported symbols, loud failure without a GPU."""
 import ctypes
+import os
 import re
 import subprocess
 from pathlib import Path
@@ -45,6 +46,65 @@ def test_library_is_built_from_these_sources():
     lib = ctypes.CDLL(str(raftsim.LIB_PATH))
     lib.raftsim_src_hash.restype = ctypes.c_char_p
     assert lib.raftsim_src_hash().decode() == _build.source_hash()
+
+
+CSRC = ROOT / "raft-simulation_amd" / "csrc"
+# the compile-time switches csrc/device.hpp declares (diagnostic builds only)
+SWITCHES = ["RS_BURST", "RS_BURST_MIN", "RS_BURST_SKIP", "RS_BURST_DIAG", "RS_WAVELOG"]
+
+
+@pytest.mark.parametrize("switch", SWITCHES)
+def test_switches_need_a_diagnostic_build(switch):
+    """Setting a kernel switch without RS_DIAG_BUILD is a compile error that names the switch
+    (preprocessing only); with RS_DIAG_BUILD it is accepted."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "-E", "--cuda-host-only", "-std=c++17", f"-D{switch}=0", "-o", os.devnull,
+           str(CSRC / "tick_kernel.hip")]
+    plain = subprocess.run(cmd, capture_output=True, text=True)
+    assert plain.returncode != 0
+    assert re.search(rf"\b{switch}\b", plain.stderr), plain.stderr
+    diag = subprocess.run(cmd + ["-DRS_DIAG_BUILD"], capture_output=True, text=True)
+    assert diag.returncode == 0, diag.stderr
+
+
+def test_embedded_hash_recognises_a_diagnostic_tag(tmp_path):
+    from raftsim import _build
+
+    f = tmp_path / "lib.so"
+    f.write_bytes(b"\x7fELF\0junk RAFTSIM_SRC_HASH=diag\0 more")
+    assert _build.embedded_hash(f) == "diag"
+    f.write_bytes(b"\x7fELF\0junk RAFTSIM_SRC_HASH=0123456789abcdef\0 more")
+    assert _build.embedded_hash(f) == "0123456789abcdef"
+
+
+def test_check_build_refuses_a_diagnostic_library(tmp_path, monkeypatch):
+    """A library tagged "diag" (built with RS_DIAG_BUILD: its results or counters may be wrong) is
+    never taken for the product; RAFTSIM_LIB, how variants are loaded, still skips the check."""
+    f = tmp_path / "libraftsim.so"
+    f.write_bytes(b"RAFTSIM_SRC_HASH=diag\0")
+    monkeypatch.setattr(raftsim, "LIB_PATH", f)
+    monkeypatch.setattr(raftsim, "_checked", [])
+    monkeypatch.delenv("RAFTSIM_LIB", raising=False)
+    with pytest.raises(raftsim.RaftSimError, match="diagnostic"):
+        raftsim.check_build()
+    assert not raftsim._checked
+    monkeypatch.setenv("RAFTSIM_LIB", str(f))
+    raftsim.check_build()
+
+
+def test_kernel_sources_name_only_the_declared_switches():
+    """Every RS_* token in the kernel sources is one of device.hpp's switches, RS_DIAG_BUILD or a
+    function-like helper macro: a new knob has to be added to the fenced block in device.hpp and
+    to this list on purpose, and a retired one cannot linger in a condition."""
+    allowed = set(SWITCHES) | {"RS_DIAG_BUILD", "RS_PLAN", "RS_SB", "RS_STORM", "RS_CFG",
+                               "RS_LANE", "RS_PHASE", "RS_PX", "RS_LPH"}
+    found = {}
+    for f in sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.hpp")):
+        for tok in re.findall(r"\bRS_[A-Z0-9_]+\b", f.read_text()):
+            found.setdefault(tok, f.name)
+    assert len(found) >= len(SWITCHES)
+    stray = {t: n for t, n in found.items() if t not in allowed}
+    assert not stray, stray
 
 
 def test_oracle_mirrors_the_abi():
