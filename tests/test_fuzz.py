@@ -103,11 +103,25 @@ def test_fuzz_gpu_lite_queues(seed):
     messages start the launch in HBM mode, short timers and fixed delays up to 6 ticks (a sender
     then finds its previous message still held: overflow cell + spill), tiny inboxes (LDS-mode
     overflow drops), halted receivers; single-tick and long launches against the oracle."""
-    rng = random.Random(11000 + seed)
+    _lite_queues(random.Random(11000 + seed), 5)
+
+
+def _lite_queues(rng, max_nodes):
     cfg = fuzz.random_config(rng)
     d = rng.choice([1, 1, 2, 3, 6])
-    cfg.update(nodes=rng.randint(2, 5), client_ppm=0, drop_ppm=0, dup_ppm=0, part_ppm=0,
+    cfg.update(nodes=rng.randint(2, max_nodes), client_ppm=0, drop_ppm=0, dup_ppm=0, part_ppm=0,
                dmin=d, dmax=d, trace_cap=0, trace_entry_cap=0,
                inbox_cap=rng.choice([1, 2, 3, 16]), variant_flags=rng.choice([0, 0, 1]))
     scns = [_no_client_sets(fuzz.random_scenario(rng, cfg)) for _ in range(200)]
     _gpu_vs_oracle_multi_tick(cfg, scns, [1, 3, 8, 64, 200, 2000])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", range(16))
+def test_fuzz_gpu_lite_queues_general(seed, monkeypatch):
+    """The same states and launches at N = 2..9 on the general body's LITE instance alone
+    (RAFTSIM_STEADY=never; at N >= 6 there is no other path): queued messages of all four
+    network types, halted receivers and random logs reach tick_kernel<N, 0, 0, LITE> at
+    N = 6..9, and at N <= 5 without the steady kernel's catch-up in between."""
+    monkeypatch.setenv("RAFTSIM_STEADY", "never")
+    _lite_queues(random.Random(13000 + seed), 9)

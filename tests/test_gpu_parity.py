@@ -146,6 +146,38 @@ CASES = {
     # d + N - 1): every round runs tick by tick, elections keep interrupting them
     "lite_short_round": dict(n_clusters=1000, nodes=5, seed=85, hb=9, el_base=6, el_span=30,
                              dmin=3, dmax=3),
+    # LITE launches at N >= 6 have no steady kernel: every launch of a fault-free, client-free
+    # handle runs the general body's LITE instance, tick_kernel<N, 0, 0, LITE> (one copy per
+    # message, the fault-free delivery pack, no PROV / RC / REGS / BURST): a fixed delay above 1;
+    # heartbeats slower than the election timer (NPE halts, messages to halted nodes); four-slot
+    # and one-slot inboxes (a leader's RES ring overflows; with one slot every vote is lost and no
+    # leader is ever elected); 7-tick delays across 13-tick launches; timers shorter than a round
+    "lite_n6": dict(n_clusters=700, nodes=6, seed=171, hb=300, el_base=500, el_span=500),
+    "lite_n7_d4": dict(n_clusters=700, nodes=7, seed=173, hb=300, el_base=500, el_span=500,
+                       dmin=4, dmax=4),
+    "lite_n8_elections": dict(n_clusters=600, nodes=8, seed=175, hb=700, el_base=500, el_span=400,
+                              dmin=3, dmax=3),
+    "lite_n9_inbox4": dict(n_clusters=512, nodes=9, seed=177, inbox_cap=4, hb=200, el_base=500,
+                           el_span=300),
+    "lite_n6_inbox1": dict(n_clusters=512, nodes=6, seed=183, inbox_cap=1, hb=40, el_base=60,
+                           el_span=40, dmin=2, dmax=2),
+    "lite_n9_odd_launches": dict(n_clusters=400, nodes=9, seed=179, ticks_per_launch=13, hb=60,
+                                 el_base=100, el_span=100, dmin=7, dmax=7),
+    "lite_n7_short_round": dict(n_clusters=512, nodes=7, seed=181, hb=9, el_base=6, el_span=30,
+                                dmin=3, dmax=3),
+    # fault-free Spec-Raft handles: DevSim::lite is set (rebuild period 8, first launch unpacked,
+    # no storm split) but the kernel is tick_kernel<N, 0, SPEC, 0>; at N = 6 the one N = 6 instance
+    # with REGS and one wave per SIMD
+    "spec_lite_n5": dict(n_clusters=700, nodes=5, seed=185, hb=300, el_base=500, el_span=500,
+                         variant_flags=2),
+    "spec_lite_n6_elections": dict(n_clusters=512, nodes=6, seed=191, hb=700, el_base=500,
+                                   el_span=400, dmin=3, dmax=3, variant_flags=2),
+    "spec_lite_n9_inbox4": dict(n_clusters=512, nodes=9, seed=193, inbox_cap=4, hb=200,
+                                el_base=500, el_span=300, variant_flags=2),
+    # a fault-free traced faithful handle, tick_kernel<6, TRACE, 0, 0> with DevSim::lite set: the
+    # 16-event trace ring wraps
+    "traced_lite_n6": dict(n_clusters=256, nodes=6, seed=189, hb=40, el_base=60, el_span=40,
+                           dmin=2, dmax=2, trace_cap=16, trace_entry_cap=8),
 }
 
 
@@ -202,13 +234,16 @@ def test_gpu_c2_full_size(seed):
     assert 0 <= bails[0] <= 2 and bails[-1] == 0, bails
 
 
-@pytest.mark.parametrize("variant,nodes", [(0, 5), (2, 5), (3, 5), (0, 9), (2, 7)])
+@pytest.mark.parametrize("variant,nodes", [(0, 5), (2, 5), (3, 5), (0, 9), (2, 7), (2, 2), (2, 4),
+                                           (2, 6), (2, 8)])
 def test_gpu_storm_window(variant, nodes):
     """The STORM body (tick_wave.hpp): a fresh handle with client traffic runs the ticks before
     el_base -- where only client-sets at followers and their redirects can happen -- as a launch of
     its own, split off the first step; digest- and counter-equal to the oracle after it and after
     the elections that follow (core.clj:151-160 with server.clj:62-63; 166-169). A host write of the
-    clock ends the storm ticks: the same step is then one launch, with the same results."""
+    clock ends the storm ticks: the same step is then one launch, with the same results. (Spec-Raft
+    at even N: no CASES entry runs tick_kernel<N, 0, SPEC, 0, STORM> there, and a handle whose
+    state the host wrote has no storm ticks, so no fuzz or known-answer test does either.)"""
     cfg = dict(n_clusters=4096, nodes=nodes, seed=11 + variant, hb=400, el_base=1500, el_span=800,
                client_ppm=300000, client_period=4096, client_burst=1024, client_redirects=4,
                log_cap=256, variant_flags=variant, drop_ppm=50000, dmin=1, dmax=20)
@@ -294,7 +329,7 @@ def _client_set_into(be, cluster, node, value):
     be.write_queue(cluster, node, 0, q + [[arr, 3, 0, value, 0, 0, 0, 0]])
 
 
-@pytest.mark.parametrize("mode", ["auto", "always"])
+@pytest.mark.parametrize("mode", ["auto", "always", "never"])
 @pytest.mark.parametrize("event", ["set_tick", "client_set", "client_cursor", "node_term",
                                    "node_log"])
 def test_gpu_host_writes_after_lite_launches(event, mode, monkeypatch):
@@ -304,7 +339,8 @@ def test_gpu_host_writes_after_lite_launches(event, mode, monkeypatch):
     left with a certificate (a follower's term raised; a log entry given to a leader and committed:
     raft_sim_write_nodes clears the certificate, device.hpp) land at every phase of the rebuild
     cycle; GPU == oracle after each of the next 10 launches (raftsim.hip: packing keys and
-    histogram stay consistent)."""
+    histogram stay consistent). With RAFTSIM_STEADY=never every launch runs the general body's
+    LITE instance, so the node writes reach it without the steady kernel's catch-up."""
     monkeypatch.setenv("RAFTSIM_STEADY", mode)
     cfg = dict(n_clusters=4096, nodes=5, seed=42, ticks_per_launch=1000, log_cap=64)
     for phase in (0, 3):
@@ -341,6 +377,104 @@ def test_gpu_host_writes_after_lite_launches(event, mode, monkeypatch):
             bad = np.nonzero(g.digest() != r.digest())[0]
             assert not len(bad), f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}"
         assert g.counters() == r.counters()
+
+
+@pytest.mark.parametrize("nodes,variant_flags,steady_mode,moved", [
+    (3, 0, "never", 0), (5, 0, "never", 0), (5, 0, "always", 0), (7, 0, None, 0), (9, 0, None, 0),
+    (6, 2, None, 0),
+    (4, 0, "never", 1), (5, 0, "always", 1), (8, 0, None, 1), (9, 0, None, 1), (6, 2, None, 1)])
+def test_gpu_host_written_logs_wrap_odd_arena(nodes, variant_flags, steady_mode, moved,
+                                              monkeypatch):
+    """Host-written logs that cross the end of an odd-sized arena, in fault-free handles: the only
+    payloads a LITE launch ever sees. After 1,500 ticks every cluster with one running leader
+    gets k entries written into that leader's arena at base = A - 1 - c % 5 (so the run wraps the
+    arena's end, A = 51 or 37: no multiple of the 8-slot chunks), the older half one term back, a
+    third of them uncommitted, a third half committed. The next heartbeats ship them: P3 copies
+    them into every follower's arena and P4 compares them one entry per round trip
+    (arena_copy<1>, W = 1) in tick_kernel<N, 0, 0, LITE> -- forced at N <= 5, the only path at
+    N >= 7 -- through the steady kernel's catch-up (always), and in the Spec-Raft N = 6 kernel.
+    The faithful leader (next-index 0) ships the entries from the second on, which an empty
+    follower appends at position 0, one off the leader's log: a log-matching violation; every
+    later heartbeat re-sends the last entry and the follower appends it again (core.clj:105-123
+    truncates nothing) until its log reaches log_cap: OVERFLOW halts inside the same kernels;
+    Spec-Raft appends each entry once. GPU == oracle after each of six more launches, and every
+    counter at the end.
+
+    moved: the other nodes' logs are moved to the arena's last slots too (base = A - 2 -
+    (c + i) % 3), and in even clusters they hold the leader's first entry. Without it only the
+    leader's arena wraps (the followers append from slot 0 and halt at log_cap <= A / 2: P3's
+    destination and the appender's side of P4's compare never cross an arena's end), and every
+    append that P4 compares across a wrap is one the leader's shifted log flags anyway: a compare
+    that wrapped either log to the wrong slot passed every case. In the even clusters the first
+    append crosses the followers' wrap and leaves logs equal to the leader's: no violation there
+    (asserted on the oracle), so a wrong compare shows as one."""
+    if steady_mode is None:
+        monkeypatch.delenv("RAFTSIM_STEADY", raising=False)
+    else:
+        monkeypatch.setenv("RAFTSIM_STEADY", steady_mode)
+    L, A, k = (16, 37, 16) if nodes == 9 else (24, 51, 10)
+    cfg = dict(n_clusters=192, nodes=nodes, seed=200 + nodes, hb=60, el_base=100, el_span=100,
+               log_cap=L, arena_cap=A, ticks_per_launch=500, commit_stream_cap=5,
+               variant_flags=variant_flags)
+    if nodes == 9:
+        cfg.update(dmin=3, dmax=3)
+    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
+    helpers.oracle_threads(r, helpers.cpu_threads())
+    g.step(1500)
+    r.step(1500)
+    assert np.array_equal(g.digest(), r.digest())
+    before = r.counters()
+    recs = r.read_nodes()
+    written = clean = 0
+    for c in range(cfg["n_clusters"]):
+        leads = [i for i in range(nodes)
+                 if recs[c * nodes + i]["role"] == 2 and recs[c * nodes + i]["fault"] == 0]
+        if len(leads) != 1:
+            continue
+        lead = leads[0]
+        written += 1
+        clean += c % 2 == 0
+        base = A - 1 - c % 5
+        for be in (g, r):
+            raw = be.read_nodes_raw(c, 1)
+            term = raw[lead].current_term
+            arena = [(0, 0)] * A
+            for j in range(k):
+                arena[(base + j) % A] = (term if j >= k // 2 else max(1, term - 1), 1000 * c + j)
+            be.write_arena(c, lead + 1, arena)
+            raw[lead].log_len = k
+            raw[lead].commit_index = (c % 3) * (k // 2)
+            raw[lead].arena_base = base
+            raw[lead].arena_frontier = base + k
+            for i in range(nodes if moved else 0):
+                if i == lead or raw[i].log_len:
+                    continue
+                fb = A - 2 - (c + i) % 3
+                raw[i].arena_base = raw[i].arena_frontier = fb
+                if c % 2 == 0:
+                    be.write_arena(c, i + 1, [(0, 0)] * fb + [arena[base % A]])
+                    raw[i].log_len = 1
+                    raw[i].arena_frontier = fb + 1
+            be.write_nodes(c, raw)
+    assert np.array_equal(g.digest(), r.digest()), "state load differs"
+    for launch in range(6):
+        g.step(500)
+        r.step(500)
+        bad = np.nonzero(g.digest() != r.digest())[0]
+        assert not len(bad), (f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}\n"
+                              + helpers.describe_cluster_diff(g, r, int(bad[0])))
+    cg, cr = g.counters(), r.counters()
+    assert cg == cr
+    # witnesses, on the oracle's counters: the written logs were shipped whole and, in the
+    # faithful model, re-appended until logs overflowed
+    assert written >= 150
+    assert cr["entries_appended"] - before["entries_appended"] >= 150 * (nodes - 1) * (k - 1)
+    if variant_flags == 0:
+        assert cr["halt_overflow"] > 0 and cr["viol_log"] > 0
+    if moved and variant_flags == 0:     # one violation per follower, in the odd clusters alone
+        assert clean >= 75 and cr["viol_log"] == (written - clean) * (nodes - 1)
+    if steady_mode is not None:
+        assert (g.diag_last_bails() >= 0) == (steady_mode == "always")
 
 
 @pytest.mark.parametrize("nodes", [7, 9])
@@ -570,3 +704,18 @@ def test_gpu_forced_steady_matches_oracle(name, monkeypatch):
     g, r = run_pair(cfg, 20000, 5000)
     assert g.counters() == r.counters()
     assert g.diag_last_bails() >= 0          # the last launch took the steady path
+
+
+@pytest.mark.parametrize("name", LITE_CASES)
+def test_gpu_forced_general_matches_oracle(name, monkeypatch):
+    """Every LITE launch at N <= 5 on the general body's LITE instance, tick_kernel<N, 0, 0, LITE>
+    (RAFTSIM_STEADY=never), from init-node: the kernel that auto mode runs only in the cool-down
+    launches after a steady launch bailed more than 1/16 of its clusters; GPU == oracle after
+    every chunk."""
+    monkeypatch.setenv("RAFTSIM_STEADY", "never")
+    cfg = CASES[name]
+    g, r = run_pair(cfg, 20000, 5000)
+    assert g.counters() == r.counters()
+    bails = g.diag_last_bails()
+    print(f"{name}: diag_last_bails {bails}")
+    assert bails == -1                       # the last launch did not take the steady path
