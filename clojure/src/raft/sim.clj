@@ -134,6 +134,39 @@
             :first-violation-tick (let [v (.getLong m 8)] (when-not (= v -1) v))
             :payload-max (.getLong m 240)})))
 
+;; raft_violation_t (24 bytes): cluster, first_tick, count[3] (election, log matching, leader
+;; completeness), kinds. No reference counterpart: the per-cluster record behind the counters.
+(def violation-size 24)
+(def ^:private viol-kinds {:election 1 :log 2 :complete 4})
+
+(defn violations
+  "The clusters the checker counted a violation for, in ascending cluster order: {:total n
+  :records [...]}, a cluster matching when it has a violation of one of `kinds` (a subset of
+  #{:election :log :complete}) and its first violation tick lies in [t-lo, t-hi). At most `cap`
+  records are copied (cap 0: the total alone); the selection runs on the device."
+  [sim kinds t-lo t-hi cap]
+  (let [mask (reduce bit-or 0 (map viol-kinds kinds))
+        m (Memory. (* violation-size (max 1 cap)))
+        total (.invokeLong (f "raft_viol_read")
+                           (object-array [(:ptr sim) (int mask) (long t-lo) (long t-hi)
+                                          (when (pos? cap) m) (int cap)]))]
+    (when (neg? total) (throw (ex-info (last-error) {:rc total})))
+    {:total total
+     :records (vec (for [i (range (min total cap)) :let [b (* i violation-size)]]
+                     {:cluster (.getInt m b)
+                      :first-tick (.getInt m (+ b 4))
+                      :election (.getInt m (+ b 8))
+                      :log (.getInt m (+ b 12))
+                      :complete (.getInt m (+ b 16))
+                      :kinds (set (for [[k bit] viol-kinds
+                                        :when (pos? (bit-and bit (.getInt m (+ b 20))))] k))}))}))
+
+(defn clear-violations!
+  "Forget every cluster's violation record (state, digests and counters are unchanged)."
+  [sim]
+  (call "raft_viol_clear" (:ptr sim))
+  sim)
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

@@ -257,6 +257,37 @@ int raft_sim_last_span(raft_sim_t* sim, double* span_ms);
 void raft_sim_destroy(raft_sim_t* sim);
 const char* raft_sim_last_error(void);
 
+/* ---- Violation records (no reference counterpart, and none in the oracle library) ----------
+ * The reference has no checker; the counters above say how often and how early the checker
+ * (SIM_SPEC §4 P4) fired in the whole handle. These calls say where: the library keeps, per
+ * cluster, the earliest tick at which a violation was counted for it and its count of each kind.
+ * Every increment of a RAFT_CTR_VIOL_* counter is one increment of one cluster's record with the
+ * same tick, so per kind the records sum to the counter and their earliest first_tick is
+ * first_violation_tick (until raft_viol_clear, which leaves the counters alone). The records are
+ * a log, not state (SIM_SPEC §6): outside the digest, untouched by raft_sim_write_* and
+ * raft_sim_set_tick, cleared only by raft_sim_create and raft_viol_clear. */
+enum raft_viol_kind { RAFT_VIOL_ELECTION = 1, RAFT_VIOL_LOG = 2, RAFT_VIOL_COMPLETE = 4 };
+
+typedef struct raft_violation {
+  uint32_t cluster;    /* handle-local index, as raft_sim_read_nodes takes it */
+  uint32_t first_tick; /* earliest tick at which any violation was counted for the cluster */
+  uint32_t count[3];   /* election safety, log matching, leader completeness */
+  uint32_t kinds;      /* raft_viol_kind bits of the nonzero counts */
+} raft_violation_t;
+
+/* The clusters with a nonzero count of a kind in kinds_mask (raft_viol_kind bits, 1..7) whose
+ * first_tick lies in [t_lo, t_hi), in ascending cluster order: the first min(total, cap) of them
+ * are written to out (which may be null when cap is 0: count only). Returns the number of matching
+ * clusters, which may exceed cap, or a negative errno (-EINVAL: kinds_mask 0 or above 7, t_lo >
+ * t_hi, null out with cap > 0; -EIO: a HIP error, or a handle poisoned by a failed step). The
+ * selection runs on the device, stream-ordered after everything enqueued: valid after
+ * raft_sim_step_async, which it waits for. */
+int64_t raft_viol_read(raft_sim_t* sim, uint32_t kinds_mask, uint64_t t_lo, uint64_t t_hi,
+                       raft_violation_t* out, uint32_t cap);
+
+/* Forget every cluster's record (counters, state and digests are unchanged). */
+int raft_viol_clear(raft_sim_t* sim);
+
 #ifdef __cplusplus
 }
 #endif

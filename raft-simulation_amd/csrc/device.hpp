@@ -125,6 +125,14 @@ struct DevSim {
   // general STORM body, and their number (device word)
   uint32_t* storm_list;
   uint32_t* storm_count;
+  // Violation records (violations_kernel.hip reads them): [C][4] = the earliest tick at which a
+  // violation was counted for the cluster (INF: none), then its election-safety, log-matching
+  // and leader-completeness counts. A log, not state: outside the digest, untouched by host
+  // writes of state and by set_tick, cleared by create and raft_viol_clear only. violation()
+  // (tick_wave.hpp) is the one writer: the storm kernel, the STORM body and the steady kernel's
+  // own rounds cannot violate (no election, no append), and the steady kernel's catch-up runs
+  // tick_wave. Last in the struct: every other field keeps its kernel-argument offset.
+  uint32_t* viol;
 };
 
 // The kernel's DevSim argument, read where a field is used. The kernels that run the tick body

@@ -19,6 +19,11 @@ hipError_t launch_init(const DevSim& S, hipStream_t st);
 hipError_t launch_digest(const DevSim& S, uint32_t c0, uint32_t nc, unsigned long long* out,
                          hipStream_t st);
 hipError_t configure_kernels();
+// violations_kernel.hip
+hipError_t launch_viol_clear(const DevSim& S, hipStream_t st);
+size_t viol_scratch_words(uint32_t C);
+hipError_t launch_viol_query(const DevSim& S, uint32_t kinds, uint64_t t_lo, uint64_t t_hi,
+                             uint32_t* scratch, void* out, uint32_t cap, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -91,6 +96,11 @@ struct Shard {
   // client-sets at followers. Any host write of state or of the clock ends it (0).
   uint32_t storm_until;
   bool storm_ran = false;              // a storm-kernel launch has run (raftsim_diag_storm_bails)
+  // raft_viol_read: the compaction's chunk counts (violations_kernel.hip), the events around its
+  // kernels (raftsim_diag_viol_ms) and their device time at the last query
+  uint32_t* vscratch;
+  hipEvent_t vev0, vev1;
+  double viol_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
 // The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
@@ -174,6 +184,8 @@ static void sh_destroy(Shard* s) {
   if (s->bail_host) (void)hipHostFree(s->bail_host);
   if (s->ev_start) (void)hipEventDestroy(s->ev_start);
   if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
+  if (s->vev0) (void)hipEventDestroy(s->vev0);
+  if (s->vev1) (void)hipEventDestroy(s->vev1);
   for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -231,7 +243,9 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
       (rc = dalloc(s, &d.tr, NN * std::max<uint32_t>(d.TC, 1) * 32)) ||
       (rc = dalloc(s, &d.tcount, NN)) ||
       (rc = dalloc(s, &d.tent, NN * std::max<uint32_t>(d.TE, 1))) ||
-      (rc = dalloc(s, &d.tecount, NN))) {
+      (rc = dalloc(s, &d.tecount, NN)) ||
+      (rc = dalloc(s, &d.viol, (size_t)s->C * 4)) ||
+      (rc = dalloc(s, &s->vscratch, rs::viol_scratch_words(s->C)))) {
     sh_destroy(s);
     return rc;
   }
@@ -299,6 +313,8 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
   if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_start)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_stop)) != hipSuccess ||
+      (e = hipEventCreate(&s->vev0)) != hipSuccess ||
+      (e = hipEventCreate(&s->vev1)) != hipSuccess ||
       (e = hipMemsetAsync(d.hot, 0, (size_t)s->C * d.HB * 4, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.qbuf, 0, NN * 2 * s->Q * 32, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.arena, 0, (NN * (size_t)s->A + rs::ARENA_PAD_SLOTS) * 8, s->stream)) != hipSuccess ||
@@ -314,6 +330,7 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
       (e = hipMemcpyAsync(s->client_pw, pw, sizeof pw, hipMemcpyHostToDevice, s->stream)) !=
           hipSuccess ||
       (e = rs::launch_init(d, s->stream)) != hipSuccess ||
+      (e = rs::launch_viol_clear(d, s->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(s->stream)) != hipSuccess) {
     sh_destroy(s);
     return fail(-EIO, "HIP error during create: %s", hipGetErrorString(e));
@@ -1063,6 +1080,99 @@ int raft_sim_read_counters(raft_sim_t* r, raft_counters_t* out) {
     out->first_violation_tick = std::min(out->first_violation_tick, c.first_violation_tick);
     out->payload_max = std::max(out->payload_max, c.payload_max);
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Violation records (include/raftsim.h, "no reference counterpart"): the compaction runs on every
+// shard's stream at once, behind whatever the shard has enqueued; shards are contiguous cluster
+// ranges, so their results concatenated in shard order are sorted, and a record's cluster is
+// rebased from the shard to the handle.
+int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64_t t_hi,
+                       raft_violation_t* out, uint32_t cap) {
+  if (!r) return fail(-EINVAL, "null sim");
+  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  if (kinds_mask == 0 || kinds_mask > 7) return fail(-EINVAL, "kinds_mask must be 1..7");
+  if (t_lo > t_hi) return fail(-EINVAL, "t_lo must be <= t_hi");
+  if (cap && !out) return fail(-EINVAL, "null output");
+  const size_t G = r->sh.size();
+  // shard d can contribute min(cap, its clusters) records at most; freed on every path below
+  std::vector<raft_violation_t*> dout(G, nullptr);
+  std::vector<uint32_t> dcap(G, 0), total(G, 0);
+  int rc = 0;
+  auto step = [&](hipError_t e, const char* what) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, what, hipGetErrorString(e));
+    return !rc;
+  };
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    dcap[d] = std::min(cap, s->C);
+    if (!step(hipSetDevice(s->cfg.device), "HIP error in raft_viol_read: %s")) break;
+    if (dcap[d] && !step(hipMalloc(reinterpret_cast<void**>(&dout[d]),
+                                   (size_t)dcap[d] * sizeof(raft_violation_t)),
+                         "hipMalloc failed in raft_viol_read: %s"))
+      break;
+    if (step(hipEventRecord(s->vev0, s->stream), "HIP error in raft_viol_read: %s") &&
+        step(rs::launch_viol_query(s->d, kinds_mask, t_lo, t_hi, s->vscratch, dout[d], dcap[d],
+                                   s->stream),
+             "HIP error in raft_viol_read: %s") &&
+        step(hipEventRecord(s->vev1, s->stream), "HIP error in raft_viol_read: %s"))
+      step(d2h(s, &total[d], s->vscratch + rs::viol_scratch_words(s->C) - 1, 1),
+           "HIP error in raft_viol_read: %s");
+  }
+  int64_t sum = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    if (!step(hipSetDevice(s->cfg.device), "HIP error in raft_viol_read: %s") ||
+        !step(hipStreamSynchronize(s->stream), "HIP error in raft_viol_read: %s"))
+      break;
+    float ms = 0;
+    if (!step(hipEventElapsedTime(&ms, s->vev0, s->vev1), "HIP error in raft_viol_read: %s")) break;
+    s->viol_ms = ms;
+    // the handle's first `cap` matches: what is left of cap after the shards before this one
+    const uint32_t left = (uint64_t)sum < cap ? cap - (uint32_t)sum : 0u;
+    const uint32_t n = std::min(std::min(total[d], dcap[d]), left);
+    if (n) {
+      raft_violation_t* dst = out + sum;
+      if (!step(hipMemcpy(dst, dout[d], (size_t)n * sizeof(raft_violation_t),
+                          hipMemcpyDeviceToHost),
+                "HIP error in raft_viol_read: %s"))
+        break;
+      for (uint32_t i = 0; i < n; ++i) dst[i].cluster += r->lo[d];
+    }
+    sum += total[d];
+  }
+  for (size_t d = 0; d < G; ++d) {
+    if (!rc && !dout[d]) continue;
+    (void)hipSetDevice(r->sh[d]->cfg.device);
+    // after an error a shard's kernels may still write dout[d] and its copy total[d]
+    if (rc) (void)hipStreamSynchronize(r->sh[d]->stream);
+    if (dout[d]) (void)hipFree(dout[d]);
+  }
+  return rc ? rc : sum;
+}
+
+int raft_viol_clear(raft_sim_t* r) {
+  if (!r) return fail(-EINVAL, "null sim");
+  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  for (Shard* s : r->sh) {
+    HIP_OK(hipSetDevice(s->cfg.device));
+    HIP_OK(rs::launch_viol_clear(s->d, s->stream));
+  }
+  for (Shard* s : r->sh) {
+    HIP_OK(hipSetDevice(s->cfg.device));
+    HIP_OK(hipStreamSynchronize(s->stream));
+  }
+  return 0;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_viol_read's kernels
+// (HIP events around them on each shard's stream), the maximum over shards, in ms.
+extern "C" int raftsim_diag_viol_ms(raft_sim_t* r, double* ms) {
+  if (!r || !ms) return fail(-EINVAL, "null argument");
+  double m = 0;
+  for (Shard* s : r->sh) m = std::max(m, s->viol_ms);
+  *ms = m;
   return 0;
 }
 

@@ -12,9 +12,22 @@
 
 namespace rs {
 
-__device__ __forceinline__ void violation(uint32_t* lctr, int kind, uint32_t t) {
+// One counted violation at tick t of the cluster with global id g: the wave's LDS counter and
+// minimum, and the cluster's record (DevSim::viol), one increment and one minimum each, so the
+// records' sums and minimum are the counters' by construction. Clusters change waves between
+// launches and the record outlives the launch, hence global memory: relaxed device-scope atomics
+// whose results are unused (the no-return forms: the lane does not wait for them). The trip loop
+// holds g for its Philox draws; the shard-local index and the record base come from kargs() here,
+// behind the rare branch, so nothing new is held across the loop (passing the local index kept it
+// and the record's offset live: +2 VGPRs in every instance, a wave per SIMD at N = 9).
+__device__ __forceinline__ void violation(uint32_t* lctr, int kind, uint32_t t, uint32_t g) {
   atomicAdd(&lctr[kind], 1u);
   atomicMin(&lctr[LCTR_FIRSTVIOL], t);
+  KDevSim* const K = kargs();
+  uint32_t* const r = K->viol + (size_t)(g - K->goff) * 4;
+  (void)__hip_atomic_fetch_min(r, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  (void)__hip_atomic_fetch_add(r + 1 + (kind - RAFT_CTR_VIOL_ELECTION), 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // LDS message cells. A node emits either one broadcast or one reply per tick, and the words
@@ -917,7 +930,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
                   const bool conf = !isL && n.len > p && pre.x == Lterm && pre.y != pv;
                   as = as + 1 == A ? 0u : as + 1;
                   if (!isL && n.len > p + 1) pre = own[as];
-                  if (p < omax && cluster_any(conf) && isL) violation(lctr, RAFT_CTR_VIOL_LOG, tc);
+                  if (p < omax && cluster_any(conf) && isL) violation(lctr, RAFT_CTR_VIOL_LOG, tc, g);
                 }
                 tc = max(tc + 1, min(min(cnext, rc ? tc + 1 : INF), min(min(Ldl, fmin), tend)));
               }
@@ -1606,7 +1619,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
             const uint32_t ls = __shfl(n.led, bl + s);
             bad |= elected && s != k && ls == n.led;
           }
-          if (bad) violation(lctr, RAFT_CTR_VIOL_ELECTION, t);
+          if (bad) violation(lctr, RAFT_CTR_VIOL_ELECTION, t, g);
         }
         if (__ballot(appended_at >= 0)) {                             // log matching
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // peers' P3 arena writes
@@ -1719,7 +1732,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
             for (int s = 0; s < N; ++s) fa |= (uint32_t)__shfl((int)found, bl + s);
           }
           const bool bad = active && ((fa >> k) & 1);
-          if (bad) violation(lctr, RAFT_CTR_VIOL_LOG, t);
+          if (bad) violation(lctr, RAFT_CTR_VIOL_LOG, t, g);
         }
         if (elected && hidx > 0) {                     // leader completeness (pre-tick hwm)
           bool ok = n.len >= hidx;
@@ -1727,7 +1740,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
             const uint2 e = sar[(n.base + hidx - 1) % A];
             ok = e.x == hterm && e.y == hval;
           }
-          if (!ok) violation(lctr, RAFT_CTR_VIOL_COMPLETE, t);
+          if (!ok) violation(lctr, RAFT_CTR_VIOL_COMPLETE, t, g);
         }
         int32_t cm = -1;
         uint32_t ct = 0, cv = 0;

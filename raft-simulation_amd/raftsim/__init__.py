@@ -13,7 +13,8 @@ from pathlib import Path
 
 from . import _build
 from ._abi import COUNTER_NAMES  # noqa: F401
-from ._backend import FAULT_NAMES, ROLE_NAMES, Backend, RaftSimError  # noqa: F401
+from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, GpuBackend,  # noqa: F401
+                       RaftSimError, replay_config)
 
 PKG_DIR = Path(__file__).resolve().parent.parent          # raft-simulation_amd/
 LIB_PATH = Path(os.environ.get("RAFTSIM_LIB", PKG_DIR / "build" / "libraftsim.so"))
@@ -41,7 +42,7 @@ def check_build():
     _checked.append(True)
 
 
-class Simulator(Backend):
+class Simulator(GpuBackend):
     """Batched simulator on the GPU (HIP kernels for gfx950)."""
 
     def __init__(self, **config):
@@ -80,3 +81,20 @@ class Simulator(Backend):
         f.restype = ctypes.c_int
         f.argtypes = [ctypes.c_void_p]
         return int(f(self._h))
+
+
+def replay(sim, cluster, ticks=None):
+    """A one-cluster Simulator that reruns cluster `cluster` of `sim` with the trace rings on
+    (sim.replay_config), stepped to `ticks` (default: sim's current tick) in sim's
+    ticks_per_launch. Closes the loop search -> violations() -> replay -> edn_trace. Only a run
+    from init-node is reproducible from its config: raises if the host ever wrote sim's state or
+    clock (write_*, set_tick)."""
+    if sim.host_written:
+        raise RaftSimError("replay: the handle's state or clock was written by the host "
+                           "(write_*, set_tick); only a run from init-node can be replayed")
+    one = Simulator(**sim.replay_config(cluster))
+    ticks = sim.tick if ticks is None else int(ticks)
+    # (results do not depend on the step size; one step runs ticks_per_launch ticks per launch)
+    if ticks:
+        one.step(ticks)
+    return one

@@ -102,6 +102,15 @@ class Counters(C.Structure):
         return d
 
 
+class Violation(C.Structure):
+    """raft_violation_t: one violating cluster (no reference counterpart)."""
+    _fields_ = [("cluster", C.c_uint32), ("first_tick", C.c_uint32), ("count", C.c_uint32 * 3),
+                ("kinds", C.c_uint32)]
+
+
+# raft_viol_kind bits, in the order of raft_violation_t.count
+VIOL_KINDS = {"election": 1, "log": 2, "complete": 4}
+
 P = C.POINTER
 _SIGS = {
     "abi_version": (C.c_int, []),
@@ -142,10 +151,21 @@ _SIGS = {
 PRODUCT_SYMBOLS = ["raft_sim_" + n for n in _SIGS]
 
 
-def bind(lib, prefix, optional=()):
+# The entry points with no reference counterpart that the oracle library does not mirror
+# (include/raftsim.h, "Violation records"): bound for the product library only, under their own
+# prefix, so PRODUCT_SYMBOLS stays the raft_sim_* set the oracle implements as raft_ref_*.
+_VIOL_SIGS = {
+    "read": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, P(Violation),
+                         C.c_uint32]),
+    "clear": (C.c_int, [C.c_void_p]),
+}
+VIOL_SYMBOLS = ["raft_viol_" + n for n in _VIOL_SIGS]
+
+
+def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in (_SIGS if sigs is None else sigs).items():
         sym = prefix + name
         if not hasattr(lib, sym):
             if name in optional:

@@ -40,6 +40,9 @@ class Backend:
         self._h = h
         self.N = self.config.nodes
         self.C = self.config.n_clusters
+        # True once the host wrote state or the clock (write_*, set_tick): such a run is no longer
+        # the one the config alone reproduces from init-node (raftsim.replay refuses it)
+        self.host_written = False
 
     # -- plumbing -------------------------------------------------------------------------------
     def _check(self, rc):
@@ -82,6 +85,7 @@ class Backend:
     def set_tick(self, tick):
         """Resume at `tick` (state restored through the write_* calls; SIM_SPEC deadlines are
         absolute ticks)."""
+        self.host_written = True
         self._check(self._fns["set_tick"](self._h, int(tick)))
 
     def last_step_timing(self):
@@ -106,6 +110,7 @@ class Backend:
         return [n.as_dict(self.N) for n in self.read_nodes_raw(c0, nc)]
 
     def write_nodes(self, c0, records):
+        self.host_written = True
         nc = len(records) // self.N
         arr = (_abi.Node * len(records))()
         for i, r in enumerate(records):
@@ -126,6 +131,7 @@ class Backend:
         return [buf[i].words() for i in range(n)]
 
     def write_queue(self, cluster, node_id, which, msgs):
+        self.host_written = True
         buf = (_abi.Msg * max(1, len(msgs)))()
         for i, w in enumerate(msgs):
             for f, v in zip(("arrival", "hdr", "term", "a", "b", "eterm", "eval", "poff"), w):
@@ -139,6 +145,7 @@ class Backend:
         return [(e.term, e.val) for e in buf]
 
     def write_arena(self, cluster, node_id, entries):
+        self.host_written = True
         buf = (_abi.Entry * max(1, len(entries)))()
         for i, (t, v) in enumerate(entries):
             buf[i].term, buf[i].val = t, v
@@ -160,6 +167,7 @@ class Backend:
         return list(buf[:n])
 
     def write_commit_stream(self, cluster, node_id, vals):
+        self.host_written = True
         buf = (C.c_uint32 * max(1, len(vals)))(*vals)
         self._check(self._fns["write_commit_stream"](self._h, cluster, node_id, buf, len(vals)))
 
@@ -222,6 +230,7 @@ class Backend:
         return [r.as_dict() for r in arr]
 
     def write_clusters(self, c0, recs):
+        self.host_written = True
         arr = (_abi.Cluster * len(recs))()
         for i, r in enumerate(recs):
             arr[i].hwm_index, arr[i].hwm_term, arr[i].hwm_val = r["hwm"]
@@ -255,3 +264,88 @@ class Backend:
                 ":leader-state": ls,
                 ":votes": {p for p in range(1, self.N + 1) if (r["votes"] >> p) & 1},
                 "halted": FAULT_NAMES[r["fault"]]}
+
+
+# The default trace rings of a replay handle: one cluster, so a few MB hold a long run's events.
+REPLAY_TRACE_CAP = 4096
+REPLAY_TRACE_ENTRY_CAP = 1 << 15
+
+
+class GpuBackend(Backend):
+    """A handle of libraftsim.so: the ABI the oracle mirrors, plus the entry points it has no
+    counterpart for (include/raftsim.h, "Violation records"): which clusters violated, which
+    invariant, when first -- and the config that replays one of them alone."""
+
+    def __init__(self, lib_path, prefix, **config):
+        super().__init__(lib_path, prefix, **config)
+        self._viol = _abi.bind(self._lib, "raft_viol_", sigs=_abi._VIOL_SIGS)
+
+    def _viol_read(self, mask, t_lo, t_hi, cap):
+        buf = (_abi.Violation * max(1, cap))()
+        n = int(self._viol["read"](self._h, mask, t_lo, t_hi, buf if cap else None, cap))
+        return self._check(n), buf
+
+    def violations(self, kinds=("election", "log", "complete"), t_lo=0, t_hi=None, limit=None):
+        """The clusters the checker counted a violation for: (total, records). A cluster matches
+        when it has a violation of one of `kinds` and its first violation tick lies in
+        [t_lo, t_hi) (t_hi None: no upper bound). `records` lists the matches in ascending cluster
+        order, the first `limit` of them when a limit is given (limit=0: the total alone), as
+        dicts: cluster (handle-local, as read_nodes takes it), global_id (cluster_offset +
+        cluster), first_tick, election / log / complete (the cluster's counts) and kinds (the
+        names of its nonzero counts). The selection runs on the device; only the records asked for
+        are copied."""
+        mask = 0
+        for k in kinds:
+            if k not in _abi.VIOL_KINDS:
+                raise ValueError(f"unknown violation kind {k!r} (one of {list(_abi.VIOL_KINDS)})")
+            mask |= _abi.VIOL_KINDS[k]
+        t_hi = 2 ** 64 - 1 if t_hi is None else int(t_hi)
+        if limit is None:
+            total, _ = self._viol_read(mask, int(t_lo), t_hi, 0)
+            cap = total
+        else:
+            cap = int(limit)
+        total, buf = self._viol_read(mask, int(t_lo), t_hi, cap)
+        off = self.config.cluster_offset
+        names = list(_abi.VIOL_KINDS)
+        recs = []
+        for v in buf[:min(total, cap)]:
+            rec = {"cluster": v.cluster, "global_id": off + v.cluster, "first_tick": v.first_tick}
+            rec.update(zip(names, v.count))
+            rec["kinds"] = tuple(n for n in names if v.kinds & _abi.VIOL_KINDS[n])
+            recs.append(rec)
+        return total, recs
+
+    def clear_violations(self):
+        """Forget every cluster's violation record (state, digests and counters are unchanged)."""
+        self._check(self._viol["clear"](self._h))
+
+    def last_violations_ms(self):
+        """Diagnostic: device time (HIP events) of the last violations() query's kernels."""
+        f = self._lib.raftsim_diag_viol_ms
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        ms = C.c_double()
+        self._check(f(self._h, C.byref(ms)))
+        return ms.value
+
+    def replay_config(self, cluster, **overrides):
+        """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster
+        `cluster` of this one alone: Philox is keyed by the global cluster id, so n_clusters=1 at
+        cluster_offset + cluster reproduces it exactly from init-node. The trace rings are on by
+        default (the `wait` trace, F3); `overrides` replace any field."""
+        return replay_config(self.config, cluster, **overrides)
+
+
+def replay_config(config, cluster, **overrides):
+    """GpuBackend.replay_config on a bare _abi.Config (needs no library)."""
+    if not 0 <= cluster < config.n_clusters:
+        raise ValueError(f"cluster {cluster} outside the handle's {config.n_clusters}")
+    cfg = {f: getattr(config, f) for f, _ in _abi.Config._fields_}
+    cfg.update(n_clusters=1, cluster_offset=config.cluster_offset + cluster, n_devices=1,
+               trace_cap=REPLAY_TRACE_CAP, trace_entry_cap=REPLAY_TRACE_ENTRY_CAP)
+    for k in overrides:
+        if k not in cfg:
+            raise TypeError(f"unknown config field {k!r}")
+    cfg.update(overrides)
+    return cfg

@@ -92,3 +92,19 @@ def first_violation_search(sim, chunk: int, max_ticks: int, reduce_min_fn=None):
         if reduce_min_fn is not None:
             fv = reduce_min_fn(fv)
     return (None if fv == NONE_TICK else fv), done, (span, kms, launches)
+
+
+def locate_first_violation(sim, reduce_min_fn=None):
+    """After first_violation_search on a GPU handle: (the job's first violation tick or None, the
+    global ids of this rank's clusters whose first violation is at that tick). The device-side
+    query (Simulator.violations with the window [tick, tick + 1)) copies only those clusters'
+    records. With `reduce_min_fn` (as in first_violation_search) the tick is the minimum over the
+    ranks, and a rank whose own first violation is later returns an empty list."""
+    fv = sim.counters()["first_violation_tick"]
+    fv = NONE_TICK if fv is None else int(fv)
+    if reduce_min_fn is not None:
+        fv = reduce_min_fn(fv)
+    if fv == NONE_TICK:
+        return None, []
+    _, recs = sim.violations(t_lo=fv, t_hi=fv + 1)
+    return fv, [r["global_id"] for r in recs]
