@@ -167,6 +167,69 @@
   (call "raft_viol_clear" (:ptr sim))
   sim)
 
+;; raft_census_t (464 bytes, 58 u64): clusters 0, nodes 8, by_class[16] 16, leaders_hist[10] 144,
+;; live_hist[10] 224, role_nodes[4] 304, fault_nodes[5] 336, then eleven scalars from 376.
+;; No reference counterpart: what state the clusters are in now, counted on the device.
+(def census-size 464)
+(def cluster-classes
+  {:no-leader 1 :one-leader 2 :multi-leader 4 :halted 8 :no-quorum 16 :same-term-leaders 32
+   :log-full 64 :candidate 128 :settled 256})
+(def ^:private class-order
+  [:no-leader :one-leader :multi-leader :halted :no-quorum :same-term-leaders :log-full :candidate
+   :settled])
+(def ^:private census-scalars
+  [:term-min :term-max :term-sum :commit-max :commit-sum :len-max :len-sum :req-queued :res-queued
+   :hwm-max :hwm-sum])
+
+(defn census
+  "The census of every cluster of the handle (raft_census_read): :by-class maps each class of
+  cluster-classes to its number of clusters, :leaders-hist / :live-hist count the clusters with
+  exactly i live leaders / live nodes, :role-nodes live nodes by :state, :fault-nodes all nodes by
+  halt code; the rest are sums and extrema over all nodes and clusters."
+  [sim]
+  (let [m (Memory. census-size)
+        n (inc (:nodes sim))
+        u64s (fn [off cnt] (vec (for [i (range cnt)] (.getLong m (+ off (* 8 i))))))]
+    (call "raft_census_read" (:ptr sim) m)
+    (merge {:clusters (.getLong m 0)
+            :nodes (.getLong m 8)
+            :by-class (zipmap class-order (u64s 16 9))
+            :leaders-hist (u64s 144 n)
+            :live-hist (u64s 224 n)
+            :role-nodes (u64s 304 4)
+            :fault-nodes (u64s 336 5)}
+           (zipmap census-scalars (u64s 376 11)))))
+
+;; raft_cluster_state_t (32 bytes): cluster 0, classes 4, leaders 8 and halted 10 (u16 masks, bit i
+;; = id i), term_max 12, term_min 16, commit_max 20, len_max 24, queued 28.
+(def cluster-state-size 32)
+
+(defn select-clusters
+  "The clusters in given state classes, in ascending cluster order (raft_census_select): {:total n
+  :records [...]}. A cluster matches when it is in one of the classes `any` (empty: no such
+  condition), in all of `all` and in none of `none` (subsets of the keys of cluster-classes). At
+  most `cap` records are copied (cap 0: the total alone); the selection runs on the device."
+  [sim any all none cap]
+  (let [mask (fn [ks] (int (reduce bit-or 0 (map cluster-classes ks))))
+        m (Memory. (* cluster-state-size (max 1 cap)))
+        total (.invokeLong (f "raft_census_select")
+                           (object-array [(:ptr sim) (mask any) (mask all) (mask none)
+                                          (when (pos? cap) m) (int cap)]))
+        ids (fn [bits] (set (filter #(bit-test bits %) (range 1 (inc (:nodes sim))))))]
+    (when (neg? total) (throw (ex-info (last-error) {:rc total})))
+    {:total total
+     :records (vec (for [i (range (min total cap)) :let [b (* i cluster-state-size)]]
+                     {:cluster (.getInt m b)
+                      :classes (set (for [[k bit] cluster-classes
+                                          :when (pos? (bit-and bit (.getInt m (+ b 4))))] k))
+                      :leaders (ids (.getShort m (+ b 8)))
+                      :halted (ids (.getShort m (+ b 10)))
+                      :term-max (.getInt m (+ b 12))
+                      :term-min (.getInt m (+ b 16))
+                      :commit-max (.getInt m (+ b 20))
+                      :len-max (.getInt m (+ b 24))
+                      :queued (.getInt m (+ b 28))}))}))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

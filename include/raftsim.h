@@ -288,6 +288,64 @@ int64_t raft_viol_read(raft_sim_t* sim, uint32_t kinds_mask, uint64_t t_lo, uint
 /* Forget every cluster's record (counters, state and digests are unchanged). */
 int raft_viol_clear(raft_sim_t* sim);
 
+/* ---- State census (no reference counterpart, none in the oracle) ---------------------------
+ * What state the clusters are in right now, answered on the device from the words
+ * raft_sim_read_nodes would decode, without copying them: a census of the whole handle, and the
+ * selection of the clusters in given state classes. A class is a predicate over a cluster's N node
+ * records (SIM_SPEC.md, "Derived, not state"). With live(k) = (fault == 0), leader(k) = live and
+ * role == RAFT_LEADER, nl the number of leaders and quorum = (N+1)>>1, or N/2+1 under
+ * RAFT_VARIANT_SPEC: */
+enum raft_cluster_class {
+  RAFT_CLS_NO_LEADER = 1,          /* nl == 0 */
+  RAFT_CLS_ONE_LEADER = 2,         /* nl == 1 */
+  RAFT_CLS_MULTI_LEADER = 4,       /* nl >= 2 */
+  RAFT_CLS_HALTED = 8,             /* some node has fault != 0 */
+  RAFT_CLS_NO_QUORUM = 16,         /* live nodes < quorum */
+  RAFT_CLS_SAME_TERM_LEADERS = 32, /* two leaders with equal current_term */
+  RAFT_CLS_LOG_FULL = 64,          /* some node (live or halted) has log_len == log_cap */
+  RAFT_CLS_CANDIDATE = 128,        /* some live node has role == RAFT_CANDIDATE */
+  RAFT_CLS_SETTLED = 256           /* nl == 1 and every live node has that leader's id as
+                                      leader_id and its term as current_term */
+};
+#define RAFT_CLS_ALL 511
+
+typedef struct raft_census {            /* every field uint64_t */
+  uint64_t clusters, nodes;
+  uint64_t by_class[16];                /* clusters with class bit b set; b >= 9: 0 */
+  uint64_t leaders_hist[RAFT_MAX_NODES + 1]; /* clusters with exactly i live leaders */
+  uint64_t live_hist[RAFT_MAX_NODES + 1];    /* clusters with exactly i live nodes */
+  uint64_t role_nodes[4];               /* live nodes by role (enum raft_role) */
+  uint64_t fault_nodes[5];              /* all nodes by fault code (enum raft_fault) */
+  uint64_t term_min, term_max, term_sum;       /* over all nodes */
+  uint64_t commit_max, commit_sum, len_max, len_sum;
+  uint64_t req_queued, res_queued;      /* sums of req_count / res_count */
+  uint64_t hwm_max, hwm_sum;            /* the checker's hwm_index per cluster */
+} raft_census_t;
+
+typedef struct raft_cluster_state {     /* 32 bytes */
+  uint32_t cluster;                     /* handle-local, as raft_sim_read_nodes takes it */
+  uint32_t classes;                     /* raft_cluster_class bits */
+  uint16_t leaders, halted;             /* bit i: id i is a live leader / is halted (as votes) */
+  uint32_t term_max, term_min, commit_max, len_max; /* over all N nodes */
+  uint32_t queued;                      /* sum of req_count + res_count */
+} raft_cluster_state_t;
+
+/* The census of every cluster of the handle, reduced over its devices (sums; MIN of term_min; MAX
+ * of the *_max fields). Both calls run on the device, stream-ordered after everything enqueued
+ * (valid after raft_sim_step_async, which they wait for), read the state only (a steady
+ * certificate stays), and give bitwise the same answer for the same state. -EINVAL: null
+ * argument; -EIO: a HIP error, or a handle poisoned by a failed step. */
+int raft_census_read(raft_sim_t* sim, raft_census_t* out);
+
+/* The clusters whose class word `classes` satisfies (any_mask == 0 || classes & any_mask) &&
+ * (classes & all_mask) == all_mask && (classes & none_mask) == 0, in ascending cluster order: the
+ * first min(total, cap) of them are written to out (which may be null when cap is 0: count only).
+ * Returns the number of matching clusters, which may exceed cap, or a negative errno (-EINVAL: a
+ * mask above RAFT_CLS_ALL, all_mask & none_mask nonzero, null out with cap > 0, null sim: refused
+ * before any device is touched; -EIO as above). */
+int64_t raft_census_select(raft_sim_t* sim, uint32_t any_mask, uint32_t all_mask,
+                           uint32_t none_mask, raft_cluster_state_t* out, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

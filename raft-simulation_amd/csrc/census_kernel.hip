@@ -1,0 +1,445 @@
+// census_kernel.hip — the state census and the selection of clusters by state class (gfx950):
+// read-only queries over the hot blocks as they stand between launches (include/raftsim.h,
+// "State census"; the classes: SIM_SPEC.md, "Derived, not state").
+//
+// Mapping: the tick kernel's. One lane per node, floor(64 / N) whole clusters per wave, so every
+// field load of a wave is one contiguous N-word run per cluster (word HOT_CW + f * N + k of the
+// block, device.hpp) and a cluster's facts are wave-native: the ballot of "live leader" shifted
+// down to the cluster's lanes is the record's `leaders` mask, its popcount the leader count. Five
+// fields are read per node (flags, term, commit, len, qmeta) and, by the census, cluster word 0
+// (the checker's hwm index): at N = 5 words 0, 23-27, 48-52 and 58-72 of the block, three of its
+// five 128-B lines. No deadline is read, so a deferred draw (FL_DRAW) only needs masking off, and
+// a block under a steady certificate holds true words in every line.
+//
+// Census: a fixed grid of workgroups strides over the wave-sized groups of clusters. Counts are
+// popcounts of ballots kept in scalar registers, sums and extrema one accumulator per lane; at the
+// end every workgroup reduces to one raft_census_t in scratch and a second, one-workgroup kernel
+// folds those. Every field is an integer sum, minimum or maximum, the only synchronisation between
+// workgroups is the launch boundary and there is no atomic anywhere: the result depends on no
+// arrival or dispatch order.
+//
+// Selection: count / scan / scatter over chunks of consecutive clusters, as violations_kernel.hip
+// does over its records (the scan kernel here is a private copy of that file's). The class word is
+// recomputed in both passes: storing it would cost a write and a read of 4 B per cluster to save
+// the second read of lines the first pass has just pulled through L2. The cluster's first lane
+// stands for it in the ballot that ranks the matches; the record's per-cluster extrema are taken
+// by shuffles over the cluster's lanes, in waves that hold a match only.
+#include "device.hpp"
+
+namespace rs {
+
+constexpr uint32_t CEN_BLOCK = 256;                  // four waves
+constexpr uint32_t CEN_WAVES = CEN_BLOCK / 64;
+constexpr uint32_t CEN_MAX_GRID = 1024;              // census workgroups (= partial records) at most
+constexpr uint32_t CEN_FOLD_BLOCK = 1024;            // the folding workgroup: 16 waves
+constexpr uint32_t CEN_ROUNDS = 16;                  // selection: wave-groups per wave and chunk
+constexpr uint32_t CEN_F = sizeof(raft_census_t) / 8;   // u64 fields of a census
+static_assert(sizeof(raft_census_t) % 8 == 0 && CEN_F <= 64, "a census is at most 64 u64 fields");
+static_assert(sizeof(raft_cluster_state_t) == 32, "raft_cluster_state_t is eight words");
+
+#define CEN_IDX(field) ((uint32_t)(offsetof(raft_census_t, field) / 8))
+
+// How field f of two censuses combines: 0 sum, 1 minimum, 2 maximum.
+__host__ __device__ inline int cen_op(uint32_t f) {
+  if (f == CEN_IDX(term_min)) return 1;
+  if (f == CEN_IDX(term_max) || f == CEN_IDX(commit_max) || f == CEN_IDX(len_max) ||
+      f == CEN_IDX(hwm_max))
+    return 2;
+  return 0;
+}
+__host__ __device__ inline uint64_t cen_unit(uint32_t f) { return cen_op(f) == 1 ? ~0ull : 0ull; }
+__host__ __device__ inline uint64_t cen_fold(uint32_t f, uint64_t a, uint64_t b) {
+  const int op = cen_op(f);
+  return op == 0 ? a + b : op == 1 ? (a < b ? a : b) : (a > b ? a : b);
+}
+
+// The wave-sized groups of CPW = floor(64 / N) clusters a shard of C clusters has.
+__host__ __device__ inline uint32_t cen_groups(uint32_t C, uint32_t N) {
+  const uint32_t CPW = 64 / N;
+  return (C + CPW - 1) / CPW;
+}
+// Selection chunks: CEN_WAVES * CEN_ROUNDS groups each, consecutive clusters.
+__host__ __device__ inline uint32_t cen_chunk_clusters(uint32_t N) {
+  return CEN_WAVES * CEN_ROUNDS * (64 / N);
+}
+__host__ __device__ inline uint32_t cen_chunks(uint32_t C, uint32_t N) {
+  const uint32_t cc = cen_chunk_clusters(N);
+  return (C + cc - 1) / cc;
+}
+
+// A lane's node and its cluster's facts (the facts are the same on every lane of the cluster).
+struct CenLane {
+  bool act;                      // the lane holds a node: its slot is a whole cluster below C
+  bool head;                     // ... and it is the cluster's first lane
+  uint32_t c, k, sh;             // cluster, node index (id - 1), the cluster's first lane
+  uint32_t role, lid, fault, term, commit, len, rq, rs;
+  uint32_t classes, leaders, live, halted;   // class bits; lane-local masks (bit k = node k)
+};
+
+__device__ __forceinline__ uint32_t cen_seg(uint64_t ballot, uint32_t sh, uint32_t seg) {
+  return (uint32_t)(ballot >> sh) & seg;
+}
+
+// Load the lane's node of group g0 (clusters g0 * CPW ...) and classify its cluster. Every lane of
+// the wave must call it (ballots and shuffles). block: the cluster's block, for the caller's own
+// loads (valid when act).
+__device__ __forceinline__ CenLane cen_load(const uint32_t* __restrict__ hot, uint32_t HB,
+                                            uint32_t N, uint32_t C, uint32_t L, uint32_t quorum,
+                                            uint32_t group, uint32_t slot, uint32_t k,
+                                            const uint32_t** block) {
+  const uint32_t CPW = 64 / N, seg = (1u << N) - 1;
+  CenLane n;
+  // group < ceil(C / CPW), so group * CPW + slot stays far below 2^32 (C * N < 2^31)
+  n.c = group * CPW + slot;
+  n.k = k;
+  n.sh = slot * N;                                   // <= 63, also on the wave's spare lanes
+  n.act = slot < CPW && n.c < C;
+  n.head = n.act && k == 0;
+  uint32_t fl = 0, qm = 0;
+  n.term = n.commit = n.len = 0;
+  const uint32_t* b = hot;
+  if (n.act) {
+    b = hot + (size_t)n.c * HB;
+    const uint32_t* p = b + HOT_CW + k;              // field f at p[f * N]
+    fl = p[HF_FLAGS * N];
+    n.term = p[HF_TERM * N];
+    n.commit = p[HF_COMMIT * N];
+    n.len = p[HF_LEN * N];
+    qm = p[HF_QMETA * N];
+  }
+  *block = b;
+  // the flags word as raft_sim_read_nodes decodes it (bit 15, FL_DRAW, is not state)
+  n.role = fl & 3;
+  n.lid = (fl >> 6) & 15;
+  n.fault = (fl >> 10) & 7;
+  n.rq = (qm >> 4) & 31;
+  n.rs = (qm >> 13) & 31;
+  const bool live = n.act && n.fault == 0;
+  const bool lead = live && n.role == RAFT_LEADER;
+  n.live = cen_seg(__ballot(live), n.sh, seg);
+  n.leaders = cen_seg(__ballot(lead), n.sh, seg);
+  n.halted = cen_seg(__ballot(n.act && n.fault != 0), n.sh, seg);
+  const uint32_t cand = cen_seg(__ballot(live && n.role == RAFT_CANDIDATE), n.sh, seg);
+  const uint32_t full = cen_seg(__ballot(n.act && n.len == L), n.sh, seg);
+  const uint32_t nl = (uint32_t)__popc(n.leaders), nlive = (uint32_t)__popc(n.live);
+  // settled: the one leader's id and term on every live node (its own lane included)
+  const uint32_t lk = n.leaders ? (uint32_t)__ffs(n.leaders) - 1 : 0u;
+  const uint32_t lterm = (uint32_t)__shfl((int)n.term, (int)min(n.sh + lk, 63u));
+  const bool off = live && !(n.lid == lk + 1 && n.term == lterm);
+  const uint32_t offs = cen_seg(__ballot(off), n.sh, seg);
+  // two leaders in one term: only waves that hold a cluster with two leaders look
+  uint32_t same = 0;
+  if (__ballot(n.act && nl >= 2)) {                  // wave-uniform
+    bool eq = false;
+    for (uint32_t j = 0; j < N; ++j) {
+      const uint32_t tj = (uint32_t)__shfl((int)n.term, (int)min(n.sh + j, 63u));
+      eq = eq || (lead && j != k && ((n.leaders >> j) & 1) && tj == n.term);
+    }
+    same = cen_seg(__ballot(eq), n.sh, seg);
+  }
+  uint32_t cls = nl == 0 ? RAFT_CLS_NO_LEADER : nl == 1 ? RAFT_CLS_ONE_LEADER : RAFT_CLS_MULTI_LEADER;
+  if (n.halted) cls |= RAFT_CLS_HALTED;
+  if (nlive < quorum) cls |= RAFT_CLS_NO_QUORUM;
+  if (same) cls |= RAFT_CLS_SAME_TERM_LEADERS;
+  if (full) cls |= RAFT_CLS_LOG_FULL;
+  if (cand) cls |= RAFT_CLS_CANDIDATE;
+  if (nl == 1 && !offs) cls |= RAFT_CLS_SETTLED;
+  n.classes = n.act ? cls : 0u;
+  return n;
+}
+
+__device__ __forceinline__ bool cen_match(uint32_t cls, uint32_t any, uint32_t all, uint32_t none) {
+  return (any == 0 || (cls & any) != 0) && (cls & all) == all && (cls & none) == 0;
+}
+
+__device__ __forceinline__ uint32_t cen_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
+
+// Wave reductions of a lane value (all 64 lanes active), uniform result.
+__device__ __forceinline__ uint64_t cen_wave_fold(uint32_t f, uint64_t x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d);
+    x = cen_fold(f, x, (uint64_t)hi << 32 | lo);
+  }
+  return x;
+}
+
+// The census of the groups this workgroup strides over: part[blockIdx.x] (CEN_F u64 fields).
+__global__ void __launch_bounds__(CEN_BLOCK)
+census_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C, uint32_t L,
+              uint32_t quorum, unsigned long long* __restrict__ part) {
+  __shared__ unsigned long long rec[CEN_WAVES][CEN_F];
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t slot = lane / N, k = lane - slot * N;
+  const uint32_t groups = cen_groups(C, N);
+  // per-lane counts, in the order of the census's leading fields (clusters, nodes, by_class,
+  // leaders_hist, live_hist, role_nodes, fault_nodes): a lane counts its own node, the cluster's
+  // first lane the cluster; constant indices only, so the array lives in registers
+  constexpr uint32_t NCNT = CEN_IDX(term_min);
+  static_assert(NCNT == 2 + 16 + 2 * (RAFT_MAX_NODES + 1) + 4 + 5 &&
+                    CEN_IDX(hwm_sum) + 1 == CEN_F && CEN_F == NCNT + 11,
+                "the counts, then eleven sums and extrema: every field is stored below");
+  uint32_t cnt[NCNT] = {};
+  // per-lane sums and extrema
+  uint64_t tsum = 0, csum = 0, lsum = 0, rqs = 0, rss = 0, hsum = 0, tmin = ~0ull;
+  uint32_t tmax = 0, cmax = 0, lmax = 0, hmax = 0;
+  for (uint32_t g = blockIdx.x * CEN_WAVES + wv; g < groups; g += gridDim.x * CEN_WAVES) {
+    const uint32_t* b;
+    const CenLane n = cen_load(hot, HB, N, C, L, quorum, g, slot, k, &b);
+    const bool live = n.act && n.fault == 0;
+    cnt[CEN_IDX(clusters)] += n.head;
+    cnt[CEN_IDX(nodes)] += n.act;
+#pragma unroll
+    for (uint32_t i = 0; i < 9; ++i) cnt[CEN_IDX(by_class) + i] += n.head && ((n.classes >> i) & 1);
+    const uint32_t nl = (uint32_t)__popc(n.leaders), nv = (uint32_t)__popc(n.live);
+#pragma unroll
+    for (uint32_t i = 0; i <= RAFT_MAX_NODES; ++i) {
+      cnt[CEN_IDX(leaders_hist) + i] += n.head && nl == i;
+      cnt[CEN_IDX(live_hist) + i] += n.head && nv == i;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) cnt[CEN_IDX(role_nodes) + i] += live && n.role == i;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) cnt[CEN_IDX(fault_nodes) + i] += n.act && n.fault == i;
+    if (n.act) {
+      tsum += n.term; csum += n.commit; lsum += n.len; rqs += n.rq; rss += n.rs;
+      tmin = min(tmin, (uint64_t)n.term); tmax = max(tmax, n.term);
+      cmax = max(cmax, n.commit); lmax = max(lmax, n.len);
+    }
+    if (n.head) {
+      const uint32_t hwm = b[hot_cl_off(N)];         // cluster word 0: the checker's hwm index
+      hsum += hwm;
+      hmax = max(hmax, hwm);
+    }
+  }
+  // the wave's record: every lane takes part in the reductions, lane 0 stores. A wave's counts
+  // stay below 2^32 (64 lanes, at most 2^18 groups per wave: C * N < 2^31 over 4,096 waves).
+  unsigned long long* r = rec[wv];
+#pragma unroll
+  for (uint32_t f = 0; f < NCNT; ++f) {
+    const uint32_t s = wave_sum(cnt[f]);
+    if (lane == 0) r[f] = s;
+  }
+  const uint64_t w_tmin = cen_wave_fold(CEN_IDX(term_min), tmin);
+  const uint64_t w_tmax = cen_wave_fold(CEN_IDX(term_max), tmax);
+  const uint64_t w_tsum = cen_wave_fold(CEN_IDX(term_sum), tsum);
+  const uint64_t w_cmax = cen_wave_fold(CEN_IDX(commit_max), cmax);
+  const uint64_t w_csum = cen_wave_fold(CEN_IDX(commit_sum), csum);
+  const uint64_t w_lmax = cen_wave_fold(CEN_IDX(len_max), lmax);
+  const uint64_t w_lsum = cen_wave_fold(CEN_IDX(len_sum), lsum);
+  const uint64_t w_rqs = cen_wave_fold(CEN_IDX(req_queued), rqs);
+  const uint64_t w_rss = cen_wave_fold(CEN_IDX(res_queued), rss);
+  const uint64_t w_hmax = cen_wave_fold(CEN_IDX(hwm_max), hmax);
+  const uint64_t w_hsum = cen_wave_fold(CEN_IDX(hwm_sum), hsum);
+  if (lane == 0) {
+    r[CEN_IDX(term_min)] = w_tmin; r[CEN_IDX(term_max)] = w_tmax; r[CEN_IDX(term_sum)] = w_tsum;
+    r[CEN_IDX(commit_max)] = w_cmax; r[CEN_IDX(commit_sum)] = w_csum;
+    r[CEN_IDX(len_max)] = w_lmax; r[CEN_IDX(len_sum)] = w_lsum;
+    r[CEN_IDX(req_queued)] = w_rqs; r[CEN_IDX(res_queued)] = w_rss;
+    r[CEN_IDX(hwm_max)] = w_hmax; r[CEN_IDX(hwm_sum)] = w_hsum;
+  }
+  __syncthreads();
+  if (threadIdx.x < CEN_F) {
+    const uint32_t f = threadIdx.x;
+    uint64_t x = rec[0][f];
+#pragma unroll
+    for (uint32_t w = 1; w < CEN_WAVES; ++w) x = cen_fold(f, x, rec[w][f]);
+    part[(size_t)blockIdx.x * CEN_F + f] = x;
+  }
+}
+
+// One workgroup: out[0 .. CEN_F) = the np partial records folded field by field.
+__global__ void __launch_bounds__(CEN_FOLD_BLOCK)
+census_fold_kernel(const unsigned long long* __restrict__ part, uint32_t np,
+                   unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long acc[CEN_FOLD_BLOCK / 64][64];
+  const uint32_t f = threadIdx.x & 63, row = threadIdx.x >> 6;
+  uint64_t x = cen_unit(f);
+  if (f < CEN_F)
+    for (uint32_t p = row; p < np; p += CEN_FOLD_BLOCK / 64)
+      x = cen_fold(f, x, part[(size_t)p * CEN_F + f]);
+  acc[row][f] = x;
+  __syncthreads();
+  if (threadIdx.x < CEN_F) {
+    for (uint32_t r = 1; r < CEN_FOLD_BLOCK / 64; ++r) x = cen_fold(f, x, acc[r][f]);
+    out[f] = x;
+  }
+}
+
+// Selection, pass 1: cnt[b] = matching clusters of chunk b. Group (i * CEN_WAVES + wave) of the
+// chunk in round i: the clusters rise with (round, wave, lane).
+__global__ void __launch_bounds__(CEN_BLOCK)
+census_count_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C,
+                    uint32_t L, uint32_t quorum, uint32_t any, uint32_t all, uint32_t none,
+                    uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t wsum[CEN_WAVES];
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t slot = lane / N, k = lane - slot * N;
+  const uint32_t g0 = blockIdx.x * (CEN_WAVES * CEN_ROUNDS);
+  uint32_t m = 0;                                    // the wave's matches (uniform)
+  for (uint32_t i = 0; i < CEN_ROUNDS; ++i) {
+    const uint32_t* b;
+    const CenLane n = cen_load(hot, HB, N, C, L, quorum, g0 + i * CEN_WAVES + wv, slot, k, &b);
+    m += cen_count(n.head && cen_match(n.classes, any, all, none));
+  }
+  if (lane == 0) wsum[wv] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < CEN_WAVES; ++w) s += wsum[w];
+    cnt[blockIdx.x] = s;
+  }
+}
+
+// Selection, pass 2 (one workgroup): cnt[0 .. nb) becomes its exclusive prefix sum, cnt[nb] the
+// total (violations_kernel.hip's scan).
+__global__ void __launch_bounds__(CEN_BLOCK)
+census_scan_kernel(uint32_t* cnt, uint32_t nb) {
+  __shared__ uint32_t wsum[CEN_WAVES];
+  __shared__ uint32_t carry_s;
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (uint32_t b0 = 0; b0 < nb; b0 += CEN_BLOCK) {
+    const uint32_t i = b0 + threadIdx.x;
+    const uint32_t v = i < nb ? cnt[i] : 0u;
+    uint32_t x = v;                                  // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = (uint32_t)__shfl_up((int)x, d);
+      if (lane >= (uint32_t)d) x += y;
+    }
+    if (lane == 63) wsum[wv] = x;
+    __syncthreads();
+    uint32_t off = carry_s, tile = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < CEN_WAVES; ++w) {
+      off += w < wv ? wsum[w] : 0u;
+      tile += wsum[w];
+    }
+    if (i < nb) cnt[i] = off + x - v;
+    __syncthreads();                                 // every thread has read carry_s and wsum
+    if (threadIdx.x == 0) carry_s += tile;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) cnt[nb] = carry_s;
+}
+
+// Selection, pass 3: the matches of chunk b go to out[off[b] ...] in cluster order, as far as cap
+// reaches. out is [cap] raft_cluster_state_t, written as two 16-byte stores by the cluster's
+// first lane.
+__global__ void __launch_bounds__(CEN_BLOCK)
+census_scatter_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C,
+                      uint32_t L, uint32_t quorum, uint32_t any, uint32_t all, uint32_t none,
+                      const uint32_t* __restrict__ off, uint4* __restrict__ out, uint32_t cap) {
+  __shared__ uint32_t wsum[2][CEN_WAVES];            // alternate: one barrier per round
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t slot = lane / N, k = lane - slot * N;
+  const uint32_t g0 = blockIdx.x * (CEN_WAVES * CEN_ROUNDS);
+  uint32_t pos = off[blockIdx.x];                    // the round's first output slot (uniform)
+  if (pos >= cap) return;                            // the whole chunk lies past the capacity
+  for (uint32_t i = 0; i < CEN_ROUNDS; ++i) {
+    const uint32_t* b;
+    const CenLane n = cen_load(hot, HB, N, C, L, quorum, g0 + i * CEN_WAVES + wv, slot, k, &b);
+    const bool m = n.head && cen_match(n.classes, any, all, none);
+    const uint64_t bal = __ballot(m);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    // the record's extrema over the cluster's N lanes, gathered by its first lane
+    uint32_t tmax = n.term, tmin = n.term, cmax = n.commit, lmax = n.len, queued = n.rq + n.rs;
+    if (bal) {                                       // wave-uniform
+      for (uint32_t j = 1; j < N; ++j) {
+        const int src = (int)min(n.sh + j, 63u);
+        const uint32_t t = (uint32_t)__shfl((int)n.term, src);
+        const uint32_t c = (uint32_t)__shfl((int)n.commit, src);
+        const uint32_t l = (uint32_t)__shfl((int)n.len, src);
+        const uint32_t q = (uint32_t)__shfl((int)(n.rq + n.rs), src);
+        tmax = max(tmax, t); tmin = min(tmin, t); cmax = max(cmax, c); lmax = max(lmax, l);
+        queued += q;
+      }
+    }
+    if (lane == 0) wsum[i & 1][wv] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t woff = 0, tile = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < CEN_WAVES; ++w) {
+      const uint32_t s = wsum[i & 1][w];
+      woff += w < wv ? s : 0u;
+      tile += s;
+    }
+    const uint32_t o = pos + woff + rank;
+    if (m && o < cap) {
+      uint4* const p = out + (size_t)o * 2;
+      // cluster, classes, leaders | halted << 16 (bit i: id i, as votes), term_max
+      p[0] = make_uint4(n.c, n.classes, (n.leaders << 1) | (n.halted << 17), tmax);
+      p[1] = make_uint4(tmin, cmax, lmax, queued);
+    }
+    pos += tile;
+  }
+}
+
+static uint32_t cen_grid(uint32_t C, uint32_t N) {
+  const uint32_t wg = (cen_groups(C, N) + CEN_WAVES - 1) / CEN_WAVES;
+  return wg < CEN_MAX_GRID ? wg : CEN_MAX_GRID;
+}
+
+// u64 words of the scratch array a shard's queries need: the census workgroups' partial records
+// and the folded census, then (as u32) the selection's chunk counts and its total.
+size_t census_scratch_words(uint32_t C, uint32_t N) {
+  return ((size_t)cen_grid(C, N) + 1) * CEN_F + ((size_t)cen_chunks(C, N) + 2) / 2;
+}
+// Where the folded census / the selection's total stand in the scratch array.
+size_t census_result_word(uint32_t C, uint32_t N) { return (size_t)cen_grid(C, N) * CEN_F; }
+static uint32_t* cen_counts(unsigned long long* scratch, uint32_t C, uint32_t N) {
+  return reinterpret_cast<uint32_t*>(scratch + ((size_t)cen_grid(C, N) + 1) * CEN_F);
+}
+const uint32_t* census_total_ptr(unsigned long long* scratch, uint32_t C, uint32_t N) {
+  return cen_counts(scratch, C, N) + cen_chunks(C, N);
+}
+
+uint32_t census_quorum(uint32_t N, uint32_t variant) {
+  return variant & RAFT_VARIANT_SPEC ? N / 2 + 1 : (N + 1) >> 1;
+}
+
+// acc <- acc folded with x, field by field (the host's reduction over shards).
+void census_init(raft_census_t* acc) {
+  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
+  for (uint32_t f = 0; f < CEN_F; ++f) a[f] = cen_unit(f);
+}
+void census_combine(raft_census_t* acc, const raft_census_t* x) {
+  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
+  const uint64_t* b = reinterpret_cast<const uint64_t*>(x);
+  for (uint32_t f = 0; f < CEN_F; ++f) a[f] = cen_fold(f, a[f], b[f]);
+}
+
+// The census of shard S: scratch[census_result_word(C, N) ...] receives its raft_census_t.
+hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream_t st) {
+  const uint32_t grid = cen_grid(S.C, S.N);
+  hipLaunchKernelGGL(census_kernel, dim3(grid), dim3(CEN_BLOCK), 0, st, (const uint32_t*)S.hot,
+                     S.HB, S.N, S.C, S.L, census_quorum(S.N, S.variant), scratch);
+  hipLaunchKernelGGL(census_fold_kernel, dim3(1), dim3(CEN_FOLD_BLOCK), 0, st,
+                     (const unsigned long long*)scratch, grid, scratch + (size_t)grid * CEN_F);
+  return hipGetLastError();
+}
+
+// The selection over shard S: *census_total_ptr receives the total, out (cap records; may be null
+// when cap is 0) the first min(total, cap) matches with shard-local cluster indices.
+hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
+                                unsigned long long* scratch, void* out, uint32_t cap,
+                                hipStream_t st) {
+  const uint32_t nb = cen_chunks(S.C, S.N), q = census_quorum(S.N, S.variant);
+  uint32_t* cnt = cen_counts(scratch, S.C, S.N);
+  const uint32_t* hot = S.hot;
+  hipLaunchKernelGGL(census_count_kernel, dim3(nb), dim3(CEN_BLOCK), 0, st, hot, S.HB, S.N, S.C,
+                     S.L, q, any, all, none, cnt);
+  hipLaunchKernelGGL(census_scan_kernel, dim3(1), dim3(CEN_BLOCK), 0, st, cnt, nb);
+  if (cap)
+    hipLaunchKernelGGL(census_scatter_kernel, dim3(nb), dim3(CEN_BLOCK), 0, st, hot, S.HB, S.N,
+                       S.C, S.L, q, any, all, none, (const uint32_t*)cnt,
+                       static_cast<uint4*>(out), cap);
+  return hipGetLastError();
+}
+
+}  // namespace rs

@@ -24,6 +24,16 @@ hipError_t launch_viol_clear(const DevSim& S, hipStream_t st);
 size_t viol_scratch_words(uint32_t C);
 hipError_t launch_viol_query(const DevSim& S, uint32_t kinds, uint64_t t_lo, uint64_t t_hi,
                              uint32_t* scratch, void* out, uint32_t cap, hipStream_t st);
+// census_kernel.hip
+size_t census_scratch_words(uint32_t C, uint32_t N);
+size_t census_result_word(uint32_t C, uint32_t N);
+const uint32_t* census_total_ptr(unsigned long long* scratch, uint32_t C, uint32_t N);
+void census_init(raft_census_t* acc);
+void census_combine(raft_census_t* acc, const raft_census_t* x);
+hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream_t st);
+hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
+                                unsigned long long* scratch, void* out, uint32_t cap,
+                                hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -101,6 +111,11 @@ struct Shard {
   uint32_t* vscratch;
   hipEvent_t vev0, vev1;
   double viol_ms;
+  // raft_census_read / raft_census_select (census_kernel.hip): their scratch and the events around
+  // their kernels (raftsim_diag_census_ms), made by the first query; the last query's device time
+  unsigned long long* cscratch;
+  hipEvent_t cev0, cev1;
+  double census_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
 // The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
@@ -186,6 +201,8 @@ static void sh_destroy(Shard* s) {
   if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
   if (s->vev0) (void)hipEventDestroy(s->vev0);
   if (s->vev1) (void)hipEventDestroy(s->vev1);
+  if (s->cev0) (void)hipEventDestroy(s->cev0);
+  if (s->cev1) (void)hipEventDestroy(s->cev1);
   for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -1172,6 +1189,133 @@ extern "C" int raftsim_diag_viol_ms(raft_sim_t* r, double* ms) {
   if (!r || !ms) return fail(-EINVAL, "null argument");
   double m = 0;
   for (Shard* s : r->sh) m = std::max(m, s->viol_ms);
+  *ms = m;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// State census (include/raftsim.h, "no reference counterpart, none in the oracle"): read-only
+// kernels over the hot blocks on every shard's stream at once, behind whatever the shard has
+// enqueued. They touch neither the state nor the host's bookkeeping of it (storm_until,
+// keys_written, the steady path choice), so a certificate stays and the next step runs as it would
+// have. The census is folded over the shards on the host; selections concatenate in shard order,
+// rebased to the handle, as raft_viol_read's do.
+static int census_prepare(Shard* s) {
+  if (s->cscratch) return 0;
+  hipError_t e;
+  if ((!s->cev0 && (e = hipEventCreate(&s->cev0)) != hipSuccess) ||
+      (!s->cev1 && (e = hipEventCreate(&s->cev1)) != hipSuccess))
+    return fail(-EIO, "HIP error in the census: %s", hipGetErrorString(e));
+  return dalloc(s, &s->cscratch, rs::census_scratch_words(s->C, s->N));   // freed by sh_destroy
+}
+
+int raft_census_read(raft_sim_t* r, raft_census_t* out) {
+  if (!r || !out) return fail(-EINVAL, "null argument");
+  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  const size_t G = r->sh.size();
+  std::vector<raft_census_t> part(G);
+  int rc = 0;
+  auto step = [&](hipError_t e) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_census_read: %s", hipGetErrorString(e));
+    return !rc;
+  };
+  size_t started = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    if (!step(hipSetDevice(s->cfg.device)) || (rc = census_prepare(s))) break;
+    ++started;
+    step(hipEventRecord(s->cev0, s->stream)) &&
+        step(rs::launch_census(s->d, s->cscratch, s->stream)) &&
+        step(hipEventRecord(s->cev1, s->stream)) &&
+        step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]),
+                 (const unsigned long long*)s->cscratch + rs::census_result_word(s->C, s->N),
+                 sizeof(raft_census_t) / 8));
+  }
+  rs::census_init(out);
+  // every started shard is waited for, also after an error: its copy writes part[d]
+  for (size_t d = 0; d < started; ++d) {
+    Shard* s = r->sh[d];
+    float ms = 0;
+    step(hipSetDevice(s->cfg.device));
+    step(hipStreamSynchronize(s->stream));
+    if (rc || !step(hipEventElapsedTime(&ms, s->cev0, s->cev1))) continue;
+    s->census_ms = ms;
+    rs::census_combine(out, &part[d]);
+  }
+  return rc;
+}
+
+int64_t raft_census_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, uint32_t none_mask,
+                           raft_cluster_state_t* out, uint32_t cap) {
+  if (!r) return fail(-EINVAL, "null sim");
+  if (any_mask > RAFT_CLS_ALL || all_mask > RAFT_CLS_ALL || none_mask > RAFT_CLS_ALL)
+    return fail(-EINVAL, "class masks must be <= RAFT_CLS_ALL (511)");
+  if (all_mask & none_mask) return fail(-EINVAL, "all_mask and none_mask share a class");
+  if (cap && !out) return fail(-EINVAL, "null output");
+  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  const size_t G = r->sh.size();
+  // shard d can contribute min(cap, its clusters) records at most; freed on every path below
+  std::vector<raft_cluster_state_t*> dout(G, nullptr);
+  std::vector<uint32_t> dcap(G, 0), total(G, 0);
+  int rc = 0;
+  auto step = [&](hipError_t e, const char* what) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, what, hipGetErrorString(e));
+    return !rc;
+  };
+  const char* const herr = "HIP error in raft_census_select: %s";
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    dcap[d] = std::min(cap, s->C);
+    if (!step(hipSetDevice(s->cfg.device), herr) || (rc = census_prepare(s))) break;
+    if (dcap[d] && !step(hipMalloc(reinterpret_cast<void**>(&dout[d]),
+                                   (size_t)dcap[d] * sizeof(raft_cluster_state_t)),
+                         "hipMalloc failed in raft_census_select: %s"))
+      break;
+    if (step(hipEventRecord(s->cev0, s->stream), herr) &&
+        step(rs::launch_census_select(s->d, any_mask, all_mask, none_mask, s->cscratch, dout[d],
+                                      dcap[d], s->stream),
+             herr) &&
+        step(hipEventRecord(s->cev1, s->stream), herr))
+      step(d2h(s, &total[d], rs::census_total_ptr(s->cscratch, s->C, s->N), 1), herr);
+  }
+  int64_t sum = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    if (!step(hipSetDevice(s->cfg.device), herr) || !step(hipStreamSynchronize(s->stream), herr))
+      break;
+    float ms = 0;
+    if (!step(hipEventElapsedTime(&ms, s->cev0, s->cev1), herr)) break;
+    s->census_ms = ms;
+    // the handle's first `cap` matches: what is left of cap after the shards before this one
+    const uint32_t left = (uint64_t)sum < cap ? cap - (uint32_t)sum : 0u;
+    const uint32_t n = std::min(std::min(total[d], dcap[d]), left);
+    if (n) {
+      raft_cluster_state_t* dst = out + sum;
+      if (!step(hipMemcpy(dst, dout[d], (size_t)n * sizeof(raft_cluster_state_t),
+                          hipMemcpyDeviceToHost),
+                herr))
+        break;
+      for (uint32_t i = 0; i < n; ++i) dst[i].cluster += r->lo[d];
+    }
+    sum += total[d];
+  }
+  for (size_t d = 0; d < G; ++d) {
+    if (!rc && !dout[d]) continue;
+    (void)hipSetDevice(r->sh[d]->cfg.device);
+    // after an error a shard's kernels may still write dout[d] and its copy total[d]
+    if (rc && r->sh[d]->stream) (void)hipStreamSynchronize(r->sh[d]->stream);
+    if (dout[d]) (void)hipFree(dout[d]);
+  }
+  return rc ? rc : sum;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_census_read's or
+// raft_census_select's kernels (HIP events around them on each shard's stream), the maximum over
+// shards, in ms.
+extern "C" int raftsim_diag_census_ms(raft_sim_t* r, double* ms) {
+  if (!r || !ms) return fail(-EINVAL, "null argument");
+  double m = 0;
+  for (Shard* s : r->sh) m = std::max(m, s->census_ms);
   *ms = m;
   return 0;
 }

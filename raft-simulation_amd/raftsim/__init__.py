@@ -86,7 +86,8 @@ class Simulator(GpuBackend):
 def replay(sim, cluster, ticks=None):
     """A one-cluster Simulator that reruns cluster `cluster` of `sim` with the trace rings on
     (sim.replay_config), stepped to `ticks` (default: sim's current tick) in sim's
-    ticks_per_launch. Closes the loop search -> violations() -> replay -> edn_trace. Only a run
+    ticks_per_launch. Closes the loop search -> violations() -> replay -> edn_trace, and works the
+    same on a cluster found by state: select() -> replay(sim, rec["cluster"]). Only a run
     from init-node is reproducible from its config: raises if the host ever wrote sim's state or
     clock (write_*, set_tick)."""
     if sim.host_written:

@@ -162,6 +162,52 @@ _VIOL_SIGS = {
 VIOL_SYMBOLS = ["raft_viol_" + n for n in _VIOL_SIGS]
 
 
+# raft_cluster_class bits (include/raftsim.h, "State census"; SIM_SPEC.md, "Derived, not state")
+CLUSTER_CLASSES = {"no_leader": 1, "one_leader": 2, "multi_leader": 4, "halted": 8,
+                   "no_quorum": 16, "same_term_leaders": 32, "log_full": 64, "candidate": 128,
+                   "settled": 256}
+CLS_ALL = 511
+
+
+class Census(C.Structure):
+    """raft_census_t: the census of a handle's clusters (no reference counterpart)."""
+    _fields_ = [("clusters", C.c_uint64), ("nodes", C.c_uint64), ("by_class", C.c_uint64 * 16),
+                ("leaders_hist", C.c_uint64 * (MAX_NODES + 1)),
+                ("live_hist", C.c_uint64 * (MAX_NODES + 1)), ("role_nodes", C.c_uint64 * 4),
+                ("fault_nodes", C.c_uint64 * 5), ("term_min", C.c_uint64),
+                ("term_max", C.c_uint64), ("term_sum", C.c_uint64), ("commit_max", C.c_uint64),
+                ("commit_sum", C.c_uint64), ("len_max", C.c_uint64), ("len_sum", C.c_uint64),
+                ("req_queued", C.c_uint64), ("res_queued", C.c_uint64), ("hwm_max", C.c_uint64),
+                ("hwm_sum", C.c_uint64)]
+
+    def as_dict(self, n_nodes):
+        d = {}
+        for f, t in self._fields_:               # the structure's order
+            v = getattr(self, f)
+            d[f] = int(v) if t is C.c_uint64 else [int(x) for x in v]
+        d["by_class"] = {k: d["by_class"][b.bit_length() - 1] for k, b in CLUSTER_CLASSES.items()}
+        d["leaders_hist"] = d["leaders_hist"][:n_nodes + 1]
+        d["live_hist"] = d["live_hist"][:n_nodes + 1]
+        return d
+
+
+class ClusterState(C.Structure):
+    """raft_cluster_state_t: one selected cluster (no reference counterpart)."""
+    _fields_ = [("cluster", C.c_uint32), ("classes", C.c_uint32), ("leaders", C.c_uint16),
+                ("halted", C.c_uint16), ("term_max", C.c_uint32), ("term_min", C.c_uint32),
+                ("commit_max", C.c_uint32), ("len_max", C.c_uint32), ("queued", C.c_uint32)]
+
+
+# The state census, like the violation records, has no oracle counterpart: bound for the product
+# library only, under its own prefix.
+_CENSUS_SIGS = {
+    "read": (C.c_int, [C.c_void_p, P(Census)]),
+    "select": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(ClusterState),
+                           C.c_uint32]),
+}
+CENSUS_SYMBOLS = ["raft_census_" + n for n in _CENSUS_SIGS]
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

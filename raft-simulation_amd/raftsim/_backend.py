@@ -274,11 +274,13 @@ REPLAY_TRACE_ENTRY_CAP = 1 << 15
 class GpuBackend(Backend):
     """A handle of libraftsim.so: the ABI the oracle mirrors, plus the entry points it has no
     counterpart for (include/raftsim.h, "Violation records"): which clusters violated, which
-    invariant, when first -- and the config that replays one of them alone."""
+    invariant, when first -- and the config that replays one of them alone; and ("State census")
+    what state the clusters are in now, counted and selected on the device."""
 
     def __init__(self, lib_path, prefix, **config):
         super().__init__(lib_path, prefix, **config)
         self._viol = _abi.bind(self._lib, "raft_viol_", sigs=_abi._VIOL_SIGS)
+        self._census = _abi.bind(self._lib, "raft_census_", sigs=_abi._CENSUS_SIGS)
 
     def _viol_read(self, mask, t_lo, t_hi, cap):
         buf = (_abi.Violation * max(1, cap))()
@@ -323,6 +325,75 @@ class GpuBackend(Backend):
     def last_violations_ms(self):
         """Diagnostic: device time (HIP events) of the last violations() query's kernels."""
         f = self._lib.raftsim_diag_viol_ms
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        ms = C.c_double()
+        self._check(f(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- state census (include/raftsim.h, "State census") ---------------------------------------
+    def census(self):
+        """What state the handle's clusters are in right now, counted on the device (one pass over
+        the hot blocks, nothing but the 464-byte result copied): a dict of raft_census_t's fields.
+        `by_class` maps every class name (_abi.CLUSTER_CLASSES; SIM_SPEC.md, "Derived, not state")
+        to the number of clusters in it; `leaders_hist[i]` / `live_hist[i]` count the clusters with
+        exactly i live leaders / live nodes (i = 0..nodes); `role_nodes` counts live nodes by
+        role, `fault_nodes` all nodes by fault code; the rest are sums and extrema over all nodes
+        (term, commit, len, queued messages) and clusters (hwm). Stream-ordered: valid after
+        step_async, which it waits for. Read-only."""
+        c = _abi.Census()
+        self._check(self._census["read"](self._h, C.byref(c)))
+        return c.as_dict(self.N)
+
+    @staticmethod
+    def _class_mask(names):
+        mask = 0
+        for k in names:
+            if k not in _abi.CLUSTER_CLASSES:
+                raise ValueError(f"unknown cluster class {k!r} (one of "
+                                 f"{list(_abi.CLUSTER_CLASSES)})")
+            mask |= _abi.CLUSTER_CLASSES[k]
+        return mask
+
+    def _census_select(self, masks, cap):
+        buf = (_abi.ClusterState * max(1, cap))()
+        n = int(self._census["select"](self._h, *masks, buf if cap else None, cap))
+        return self._check(n), buf
+
+    def select(self, any=(), all=(), none=(), limit=None):
+        """The clusters in given state classes: (total, records). A cluster matches when it is in
+        one of the classes `any` (empty: no such condition), in every class of `all` and in no
+        class of `none` (names of _abi.CLUSTER_CLASSES). `records` lists the matches in ascending
+        cluster order, the first `limit` of them when a limit is given (limit=0: the total alone),
+        as dicts: cluster (handle-local, as read_nodes takes it), global_id (cluster_offset +
+        cluster), classes (the names of all the cluster's classes), leaders and halted (lists of
+        node ids), term_max, term_min, commit_max, len_max (over all its nodes) and queued
+        (messages in its queues). The selection runs on the device; only the records asked for are
+        copied. On a run from init-node, raftsim.replay(sim, rec["cluster"]) reruns a selected
+        cluster alone with its `wait` trace."""
+        masks = [self._class_mask(x) for x in (any, all, none)]
+        if limit is None:
+            total, _ = self._census_select(masks, 0)
+            cap = total
+        else:
+            cap = int(limit)
+        total, buf = self._census_select(masks, cap)
+        off = self.config.cluster_offset
+        ids = range(1, self.N + 1)
+        recs = []
+        for v in buf[:min(total, cap)]:
+            recs.append({
+                "cluster": v.cluster, "global_id": off + v.cluster,
+                "classes": tuple(k for k, b in _abi.CLUSTER_CLASSES.items() if v.classes & b),
+                "leaders": [i for i in ids if (v.leaders >> i) & 1],
+                "halted": [i for i in ids if (v.halted >> i) & 1],
+                "term_max": v.term_max, "term_min": v.term_min, "commit_max": v.commit_max,
+                "len_max": v.len_max, "queued": v.queued})
+        return total, recs
+
+    def last_census_ms(self):
+        """Diagnostic: device time (HIP events) of the last census() or select() query's kernels."""
+        f = self._lib.raftsim_diag_census_ms
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         ms = C.c_double()

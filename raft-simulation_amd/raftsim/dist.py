@@ -41,6 +41,37 @@ def reduce_counters(c: dict, device=None) -> dict:
     return out
 
 
+def reduce_census(c: dict, device=None) -> dict:
+    """All-reduce a census dict (Simulator.census()) over the default process group: SUM of the
+    counts and sums (the histograms and per-class counts element by element), MIN of term_min, MAX
+    of the *_max fields. Every rank must hold a census of the same `nodes` per cluster."""
+    import torch
+    import torch.distributed as dist
+
+    maxes = sorted(k for k in c if k.endswith("_max"))
+    lists = sorted(k for k, v in c.items() if isinstance(v, list))
+    classes = list(c["by_class"])
+    sums = sorted(k for k, v in c.items()
+                  if k not in maxes and k != "term_min" and not isinstance(v, (list, dict)))
+    flat = [int(c[k]) for k in sums] + [int(c["by_class"][k]) for k in classes]
+    for k in lists:
+        flat += [int(x) for x in c[k]]
+    v = torch.tensor(flat, dtype=torch.int64, device=device)
+    dist.all_reduce(v, op=dist.ReduceOp.SUM)
+    mx = torch.tensor([int(c[k]) for k in maxes], dtype=torch.int64, device=device)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    mn = torch.tensor([int(c["term_min"])], dtype=torch.int64, device=device)
+    dist.all_reduce(mn, op=dist.ReduceOp.MIN)
+    it = iter(int(x) for x in v.tolist())
+    out = {k: next(it) for k in sums}
+    out["by_class"] = {k: next(it) for k in classes}
+    for k in lists:
+        out[k] = [next(it) for _ in c[k]]
+    out.update(zip(maxes, (int(x) for x in mx.tolist())))
+    out["term_min"] = int(mn.item())
+    return {k: out[k] for k in c}
+
+
 def reduce_max(x: float, device=None) -> float:
     import torch
     import torch.distributed as dist

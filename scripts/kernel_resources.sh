@@ -1,4 +1,5 @@
-# Registers, scratch and occupancy of every tick-kernel instantiation as the compiler reports them
+# Registers, scratch and occupancy of every tick-kernel instantiation, and of the census kernels
+# after them, as the compiler reports them
 # (ISA comments of hipcc -S), written to profiles/TAG_kernel_resources.txt. rocprofv3's
 # VGPR_Count column uses a different encoding; these are the compiler's own counts.
 # Usage: bash scripts/kernel_resources.sh TAG
@@ -7,13 +8,16 @@ TAG=${1:-r12}
 R=$(cd "$(dirname "$0")/.." && pwd)
 S=$(mktemp /tmp/tick_kernel_XXXX.s)
 S2=$(mktemp /tmp/steady_kernel_XXXX.s)
+S3=$(mktemp /tmp/census_kernel_XXXX.s)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S \
   $R/raft-simulation_amd/csrc/tick_kernel.hip 2>/dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S2 \
   $R/raft-simulation_amd/csrc/steady_kernel.hip 2>/dev/null
-python3 - "$S" "$S2" > $R/profiles/${TAG}_kernel_resources.txt <<'PY'
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S3 \
+  $R/raft-simulation_amd/csrc/census_kernel.hip 2>/dev/null
+python3 - "$S" "$S2" "$S3" > $R/profiles/${TAG}_kernel_resources.txt <<'PY'
 import re, sys
-s = open(sys.argv[1]).read() + open(sys.argv[2]).read()
+s = open(sys.argv[1]).read() + open(sys.argv[2]).read() + open(sys.argv[3]).read()
 print(f"{'kernel':48s} {'VGPRs':>5s} {'SGPRs':>5s} {'scratch':>7s} {'waves/SIMD':>10s}")
 for m in re.finditer(r'^(_ZN2rs\w+):\s', s, re.M):
     name = m.group(1)
@@ -28,7 +32,10 @@ for m in re.finditer(r'^(_ZN2rs\w+):\s', s, re.M):
     ml = re.match(r'rs::18steady_lane_kernelILi(\d)E', pretty)
     if ml:
         pretty = f"steady_lane_kernel<N={ml.group(1)}>"
+    mc = re.match(r'rs::\d+(census_\w*?kernel)E', pretty)
+    if mc:
+        pretty = mc.group(1)
     print(f"{pretty[:48]:48s} {get('NumVgprs'):>5s} {get('TotalNumSgprs'):>5s} {get('ScratchSize'):>7s} {get('Occupancy'):>10s}")
 PY
-rm -f $S $S2
+rm -f $S $S2 $S3
 cat $R/profiles/${TAG}_kernel_resources.txt
