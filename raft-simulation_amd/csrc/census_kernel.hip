@@ -18,17 +18,18 @@
 // workgroups is the launch boundary and there is no atomic anywhere: the result depends on no
 // arrival or dispatch order.
 //
-// Selection: count / scan / scatter over chunks of consecutive clusters, as violations_kernel.hip
-// does over its records (the scan kernel here is a private copy of that file's). The class word is
-// recomputed in both passes: storing it would cost a write and a read of 4 B per cluster to save
-// the second read of lines the first pass has just pulled through L2. The cluster's first lane
-// stands for it in the ballot that ranks the matches; the record's per-cluster extrema are taken
-// by shuffles over the cluster's lanes, in waves that hold a match only.
-#include "device.hpp"
+// Selection: the compaction of compact.hpp (count / scan / scatter over chunks of consecutive
+// clusters, the one the violation query runs over its records) over the source at the end of this
+// file. The class word is recomputed in both passes: storing it would cost a write and a read of
+// 4 B per cluster to save the second read of lines the first pass has just pulled through L2. The
+// cluster's first lane stands for it in the ballot that ranks the matches; the record's
+// per-cluster extrema are taken by shuffles over the cluster's lanes, in waves that hold a match
+// only.
+#include "compact.hpp"
 
 namespace rs {
 
-constexpr uint32_t CEN_BLOCK = 256;                  // four waves
+constexpr uint32_t CEN_BLOCK = COMPACT_BLOCK;        // four waves, also for the census proper
 constexpr uint32_t CEN_WAVES = CEN_BLOCK / 64;
 constexpr uint32_t CEN_MAX_GRID = 1024;              // census workgroups (= partial records) at most
 constexpr uint32_t CEN_FOLD_BLOCK = 1024;            // the folding workgroup: 16 waves
@@ -108,12 +109,11 @@ __device__ __forceinline__ CenLane cen_load(const uint32_t* __restrict__ hot, ui
     qm = p[HF_QMETA * N];
   }
   *block = b;
-  // the flags word as raft_sim_read_nodes decodes it (bit 15, FL_DRAW, is not state)
-  n.role = fl & 3;
-  n.lid = (fl >> 6) & 15;
-  n.fault = (fl >> 10) & 7;
-  n.rq = (qm >> 4) & 31;
-  n.rs = (qm >> 13) & 31;
+  n.role = fl_role(fl);                              // bit 15, FL_DRAW, is not state
+  n.lid = fl_lid(fl);
+  n.fault = fl_fault(fl);
+  n.rq = qm_req_cnt(qm);
+  n.rs = qm_res_cnt(qm);
   const bool live = n.act && n.fault == 0;
   const bool lead = live && n.role == RAFT_LEADER;
   n.live = cen_seg(__ballot(live), n.sh, seg);
@@ -151,8 +151,6 @@ __device__ __forceinline__ CenLane cen_load(const uint32_t* __restrict__ hot, ui
 __device__ __forceinline__ bool cen_match(uint32_t cls, uint32_t any, uint32_t all, uint32_t none) {
   return (any == 0 || (cls & any) != 0) && (cls & all) == all && (cls & none) == 0;
 }
-
-__device__ __forceinline__ uint32_t cen_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 
 // Wave reductions of a lane value (all 64 lanes active), uniform result.
 __device__ __forceinline__ uint64_t cen_wave_fold(uint32_t f, uint64_t x) {
@@ -208,7 +206,7 @@ census_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_
       cmax = max(cmax, n.commit); lmax = max(lmax, n.len);
     }
     if (n.head) {
-      const uint32_t hwm = b[hot_cl_off(N)];         // cluster word 0: the checker's hwm index
+      const uint32_t hwm = b[CL_HWM_IDX];
       hsum += hwm;
       hmax = max(hmax, hwm);
     }
@@ -267,118 +265,55 @@ census_fold_kernel(const unsigned long long* __restrict__ part, uint32_t np,
   }
 }
 
-// Selection, pass 1: cnt[b] = matching clusters of chunk b. Group (i * CEN_WAVES + wave) of the
-// chunk in round i: the clusters rise with (round, wave, lane).
-__global__ void __launch_bounds__(CEN_BLOCK)
-census_count_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C,
-                    uint32_t L, uint32_t quorum, uint32_t any, uint32_t all, uint32_t none,
-                    uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t wsum[CEN_WAVES];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t slot = lane / N, k = lane - slot * N;
-  const uint32_t g0 = blockIdx.x * (CEN_WAVES * CEN_ROUNDS);
-  uint32_t m = 0;                                    // the wave's matches (uniform)
-  for (uint32_t i = 0; i < CEN_ROUNDS; ++i) {
-    const uint32_t* b;
-    const CenLane n = cen_load(hot, HB, N, C, L, quorum, g0 + i * CEN_WAVES + wv, slot, k, &b);
-    m += cen_count(n.head && cen_match(n.classes, any, all, none));
-  }
-  if (lane == 0) wsum[wv] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < CEN_WAVES; ++w) s += wsum[w];
-    cnt[blockIdx.x] = s;
-  }
-}
+// The selection's source for the compaction (compact.hpp): group (round * CEN_WAVES + wave) of the
+// chunk in round `round`, so the clusters rise with (round, wave, lane); the cluster's first lane
+// holds its item. out is [cap] raft_cluster_state_t, written as two 16-byte stores.
+struct cen_select {
+  static constexpr uint32_t ROUNDS = CEN_ROUNDS;
+  struct Item {
+    CenLane n;
+    uint32_t tmax, tmin, cmax, lmax, queued;         // the lane's own, after gather the cluster's
+  };
+  const uint32_t* __restrict__ hot;
+  uint32_t HB, N, C, L, quorum, any, all, none;
+  uint4* __restrict__ out;
 
-// Selection, pass 2 (one workgroup): cnt[0 .. nb) becomes its exclusive prefix sum, cnt[nb] the
-// total (violations_kernel.hip's scan).
-__global__ void __launch_bounds__(CEN_BLOCK)
-census_scan_kernel(uint32_t* cnt, uint32_t nb) {
-  __shared__ uint32_t wsum[CEN_WAVES];
-  __shared__ uint32_t carry_s;
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < nb; b0 += CEN_BLOCK) {
-    const uint32_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? cnt[i] : 0u;
-    uint32_t x = v;                                  // inclusive scan inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-      if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wsum[wv] = x;
-    __syncthreads();
-    uint32_t off = carry_s, tile = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < CEN_WAVES; ++w) {
-      off += w < wv ? wsum[w] : 0u;
-      tile += wsum[w];
-    }
-    if (i < nb) cnt[i] = off + x - v;
-    __syncthreads();                                 // every thread has read carry_s and wsum
-    if (threadIdx.x == 0) carry_s += tile;
-    __syncthreads();
+  __host__ __device__ uint32_t chunks() const { return cen_chunks(C, N); }
+  __device__ __forceinline__ Item load(uint32_t b, uint32_t i) const {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t slot = lane / N, k = lane - slot * N;
+    const uint32_t* blk;
+    Item it;
+    it.n = cen_load(hot, HB, N, C, L, quorum, (b * ROUNDS + i) * CEN_WAVES + wv, slot, k, &blk);
+    const CenLane& n = it.n;
+    it.tmax = it.tmin = n.term; it.cmax = n.commit; it.lmax = n.len; it.queued = n.rq + n.rs;
+    return it;
   }
-  if (threadIdx.x == 0) cnt[nb] = carry_s;
-}
-
-// Selection, pass 3: the matches of chunk b go to out[off[b] ...] in cluster order, as far as cap
-// reaches. out is [cap] raft_cluster_state_t, written as two 16-byte stores by the cluster's
-// first lane.
-__global__ void __launch_bounds__(CEN_BLOCK)
-census_scatter_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C,
-                      uint32_t L, uint32_t quorum, uint32_t any, uint32_t all, uint32_t none,
-                      const uint32_t* __restrict__ off, uint4* __restrict__ out, uint32_t cap) {
-  __shared__ uint32_t wsum[2][CEN_WAVES];            // alternate: one barrier per round
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t slot = lane / N, k = lane - slot * N;
-  const uint32_t g0 = blockIdx.x * (CEN_WAVES * CEN_ROUNDS);
-  uint32_t pos = off[blockIdx.x];                    // the round's first output slot (uniform)
-  if (pos >= cap) return;                            // the whole chunk lies past the capacity
-  for (uint32_t i = 0; i < CEN_ROUNDS; ++i) {
-    const uint32_t* b;
-    const CenLane n = cen_load(hot, HB, N, C, L, quorum, g0 + i * CEN_WAVES + wv, slot, k, &b);
-    const bool m = n.head && cen_match(n.classes, any, all, none);
-    const uint64_t bal = __ballot(m);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-    // the record's extrema over the cluster's N lanes, gathered by its first lane
-    uint32_t tmax = n.term, tmin = n.term, cmax = n.commit, lmax = n.len, queued = n.rq + n.rs;
-    if (bal) {                                       // wave-uniform
-      for (uint32_t j = 1; j < N; ++j) {
-        const int src = (int)min(n.sh + j, 63u);
-        const uint32_t t = (uint32_t)__shfl((int)n.term, src);
-        const uint32_t c = (uint32_t)__shfl((int)n.commit, src);
-        const uint32_t l = (uint32_t)__shfl((int)n.len, src);
-        const uint32_t q = (uint32_t)__shfl((int)(n.rq + n.rs), src);
-        tmax = max(tmax, t); tmin = min(tmin, t); cmax = max(cmax, c); lmax = max(lmax, l);
-        queued += q;
-      }
-    }
-    if (lane == 0) wsum[i & 1][wv] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t woff = 0, tile = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < CEN_WAVES; ++w) {
-      const uint32_t s = wsum[i & 1][w];
-      woff += w < wv ? s : 0u;
-      tile += s;
-    }
-    const uint32_t o = pos + woff + rank;
-    if (m && o < cap) {
-      uint4* const p = out + (size_t)o * 2;
-      // cluster, classes, leaders | halted << 16 (bit i: id i, as votes), term_max
-      p[0] = make_uint4(n.c, n.classes, (n.leaders << 1) | (n.halted << 17), tmax);
-      p[1] = make_uint4(tmin, cmax, lmax, queued);
-    }
-    pos += tile;
+  __device__ __forceinline__ bool match(const Item& it) const {
+    return it.n.head && cen_match(it.n.classes, any, all, none);
   }
-}
+  // the record's extrema and sum over the cluster's N lanes, gathered by its first lane
+  __device__ __forceinline__ void gather(Item& it) const {
+    const CenLane& n = it.n;
+    for (uint32_t j = 1; j < N; ++j) {
+      const int src = (int)min(n.sh + j, 63u);
+      const uint32_t t = (uint32_t)__shfl((int)n.term, src);
+      const uint32_t c = (uint32_t)__shfl((int)n.commit, src);
+      const uint32_t l = (uint32_t)__shfl((int)n.len, src);
+      const uint32_t q = (uint32_t)__shfl((int)(n.rq + n.rs), src);
+      it.tmax = max(it.tmax, t); it.tmin = min(it.tmin, t);
+      it.cmax = max(it.cmax, c); it.lmax = max(it.lmax, l);
+      it.queued += q;
+    }
+  }
+  __device__ __forceinline__ void store(const Item& it, uint32_t o) const {
+    const CenLane& n = it.n;
+    uint4* const p = out + (size_t)o * 2;
+    // cluster, classes, leaders | halted << 16 (bit i: id i, as votes), term_max
+    p[0] = make_uint4(n.c, n.classes, (n.leaders << 1) | (n.halted << 17), it.tmax);
+    p[1] = make_uint4(it.tmin, it.cmax, it.lmax, it.queued);
+  }
+};
 
 static uint32_t cen_grid(uint32_t C, uint32_t N) {
   const uint32_t wg = (cen_groups(C, N) + CEN_WAVES - 1) / CEN_WAVES;
@@ -386,9 +321,9 @@ static uint32_t cen_grid(uint32_t C, uint32_t N) {
 }
 
 // u64 words of the scratch array a shard's queries need: the census workgroups' partial records
-// and the folded census, then (as u32) the selection's chunk counts and its total.
+// and the folded census, then (as u32) the selection's compaction scratch.
 size_t census_scratch_words(uint32_t C, uint32_t N) {
-  return ((size_t)cen_grid(C, N) + 1) * CEN_F + ((size_t)cen_chunks(C, N) + 2) / 2;
+  return ((size_t)cen_grid(C, N) + 1) * CEN_F + (compact_scratch_words(cen_chunks(C, N)) + 1) / 2;
 }
 // Where the folded census / the selection's total stand in the scratch array.
 size_t census_result_word(uint32_t C, uint32_t N) { return (size_t)cen_grid(C, N) * CEN_F; }
@@ -396,7 +331,7 @@ static uint32_t* cen_counts(unsigned long long* scratch, uint32_t C, uint32_t N)
   return reinterpret_cast<uint32_t*>(scratch + ((size_t)cen_grid(C, N) + 1) * CEN_F);
 }
 const uint32_t* census_total_ptr(unsigned long long* scratch, uint32_t C, uint32_t N) {
-  return cen_counts(scratch, C, N) + cen_chunks(C, N);
+  return compact_total_ptr(cen_counts(scratch, C, N), cen_chunks(C, N));
 }
 
 uint32_t census_quorum(uint32_t N, uint32_t variant) {
@@ -429,17 +364,9 @@ hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream
 hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
                                 unsigned long long* scratch, void* out, uint32_t cap,
                                 hipStream_t st) {
-  const uint32_t nb = cen_chunks(S.C, S.N), q = census_quorum(S.N, S.variant);
-  uint32_t* cnt = cen_counts(scratch, S.C, S.N);
-  const uint32_t* hot = S.hot;
-  hipLaunchKernelGGL(census_count_kernel, dim3(nb), dim3(CEN_BLOCK), 0, st, hot, S.HB, S.N, S.C,
-                     S.L, q, any, all, none, cnt);
-  hipLaunchKernelGGL(census_scan_kernel, dim3(1), dim3(CEN_BLOCK), 0, st, cnt, nb);
-  if (cap)
-    hipLaunchKernelGGL(census_scatter_kernel, dim3(nb), dim3(CEN_BLOCK), 0, st, hot, S.HB, S.N,
-                       S.C, S.L, q, any, all, none, (const uint32_t*)cnt,
-                       static_cast<uint4*>(out), cap);
-  return hipGetLastError();
+  const cen_select src = {S.hot, S.HB, S.N, S.C, S.L, census_quorum(S.N, S.variant),
+                          any, all, none, static_cast<uint4*>(out)};
+  return launch_compact(src, cen_counts(scratch, S.C, S.N), cap, st);
 }
 
 }  // namespace rs

@@ -1,11 +1,12 @@
 // device.hpp — device-side building blocks of the tick kernel (gfx950 / CDNA4).
 //
 // Layout in HBM (node index gi = cluster * N + k, k = id - 1):
-//   hot state        hot[c][HB]: one 128-B-aligned block per cluster holding every per-node word
-//                    the tick kernel loads at launch start and stores at its end, field-major
-//                    inside the block (word f * N + k = field f of node k; fields HotField below,
-//                    next_index / match_index as N fields each), then the cluster's 8 words
-//                    (raft_cluster_t: hwm index, term, val, client_next, client_count, 0, 0, 0).
+//   hot state        hot[c][HB]: one 128-B-aligned block per cluster: the cluster's 8 words
+//                    (ClusterWord below: hwm index, term, val, client_next, client_count, two
+//                    reserved, the steady certificate), then every per-node word the tick kernel
+//                    loads at launch start and stores at its end, field-major (word HOT_CW + f * N
+//                    + k = field f of node k; fields HotField below, next_index / match_index as N
+//                    fields each).
 //                    A wave's clusters come from the packing permutation, i.e. from anywhere in
 //                    the shard: a block per cluster makes the wave's state load touch only its own
 //                    clusters' lines (the structure-of-arrays layout read ~13 lines per load)
@@ -90,7 +91,7 @@ struct DevSim {
   uint32_t hb, el_base, el_span, drop_ppm, dup_ppm, dmin, dmax, part_ppm, part_epoch,
       client_ppm, variant, client_period, client_burst, client_redirects;
   DivU32 div_period, div_burst, div_epoch;   // client_period (when > 0), client_burst, part_epoch
-  uint32_t* hot;          // [C][HB] cluster blocks (HotField, hot_cl_off, hot_block_words)
+  uint32_t* hot;          // [C][HB] cluster blocks (HotField, ClusterWord, hot_block_words)
   uint32_t HB;            // hot_block_words(N)
   uint32_t* qbuf;         // REQ [Q][NN][8], then RES [NN][Q][8]
   uint32_t* arena;        // [NN][A][2]
@@ -151,7 +152,7 @@ __device__ __forceinline__ DivU32 kdiv(const __attribute__((address_space(4))) D
   return DivU32{v.d, v.m, v.s1, v.s2};
 }
 
-// A cluster block: the cluster's 8 words (hot_cl_off = 0), then the node fields, field-major
+// A cluster block: the cluster's HOT_CW words (ClusterWord), then the node fields, field-major
 // (word HOT_CW + f * N + k is field f of node k): the HotField fields, next_index of peer id p as
 // field HF_NEXT + p - 1, match_index as HF_NEXT + N + p - 1, then the arena cursors and the
 // last-led term (hf_abase / hf_afront / hf_led). Blocks are whole 128-B lines. The order puts what
@@ -165,7 +166,6 @@ enum HotField : uint32_t {
 __host__ __device__ constexpr uint32_t hf_abase(uint32_t N) { return HF_NEXT + 2 * N; }
 __host__ __device__ constexpr uint32_t hf_afront(uint32_t N) { return HF_NEXT + 2 * N + 1; }
 __host__ __device__ constexpr uint32_t hf_led(uint32_t N) { return HF_NEXT + 2 * N + 2; }
-__host__ __device__ constexpr uint32_t hot_cl_off(uint32_t) { return 0; }
 __host__ __device__ constexpr uint32_t hot_block_words(uint32_t N) {
   return (HOT_CW + (hf_led(N) + 1) * N + 31) & ~31u;
 }
@@ -174,7 +174,7 @@ __device__ __forceinline__ uint32_t* hot_node(const DevSim& S, uint32_t c, uint3
   return S.hot + (size_t)c * S.HB + HOT_CW + k;
 }
 __device__ __forceinline__ uint32_t* hot_cl(const DevSim& S, uint32_t c) {
-  return S.hot + (size_t)c * S.HB + hot_cl_off(S.N);
+  return S.hot + (size_t)c * S.HB;
 }
 
 constexpr uint32_t SCHED_BUCKETS = 16384;   // keys clamp to SCHED_BUCKETS - 1
@@ -342,6 +342,9 @@ constexpr uint32_t FL_DRAW = 1u << 15;
 // writer of a block clears it: the general tick body's write-back, raft_sim_write_nodes,
 // raft_sim_write_queue and raft_sim_write_clusters (whose reserved words it is; reads return them
 // zeroed), and the init kernel.
+// The cluster's other words are raft_cluster_t's: the checker's high-water mark (index, term, val)
+// and the client's next injection tick and count. Words 5 and 6 are unused.
+enum ClusterWord : uint32_t { CL_HWM_IDX, CL_HWM_TERM, CL_HWM_VAL, CL_CLIENT_NEXT, CL_CLIENT_COUNT };
 constexpr uint32_t CL_CERT = 7;
 constexpr uint32_t CERT_MAGIC = 0x5EAD0000u;
 __host__ __device__ __forceinline__ uint32_t exact_deadline(uint32_t g, uint32_t id, uint32_t lb,
@@ -357,16 +360,44 @@ __device__ __forceinline__ uint4 event_draw(uint32_t g, uint32_t id, uint32_t t,
 }
 
 // Flags word: role 0-1 | voted_for 2-5 | leader_id 6-9 | fault 10-12 | is_seq 13 | ls_present 14
-__host__ __device__ __forceinline__ uint32_t pack_flags(uint32_t role, uint32_t vf, uint32_t lid,
-                                                        uint32_t fault, uint32_t seq,
-                                                        uint32_t lsp) {
+// (bit 15 is FL_DRAW). The masks are for tests and updates of several fields in place.
+constexpr uint32_t FL_ROLE = 3u, FL_VF = 15u << 2, FL_LID = 15u << 6, FL_FAULT = 7u << 10,
+                   FL_SEQ = 1u << 13, FL_LSP = 1u << 14;
+// what stepping down to follow a leader sets (steady_kernel.hip): follower, no vote, its id, a vector log
+constexpr uint32_t FL_FOLLOW = FL_ROLE | FL_VF | FL_LID | FL_SEQ;
+__host__ __device__ __forceinline__ constexpr uint32_t pack_flags(uint32_t role, uint32_t vf,
+                                                                  uint32_t lid, uint32_t fault,
+                                                                  uint32_t seq, uint32_t lsp) {
   return role | vf << 2 | lid << 6 | fault << 10 | seq << 13 | lsp << 14;
 }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_role(uint32_t fl) { return fl & 3; }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_vf(uint32_t fl) { return (fl >> 2) & 15; }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_lid(uint32_t fl) { return (fl >> 6) & 15; }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_fault(uint32_t fl) { return (fl >> 10) & 7; }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_seq(uint32_t fl) { return (fl >> 13) & 1; }
+__host__ __device__ __forceinline__ constexpr uint32_t fl_lsp(uint32_t fl) { return (fl >> 14) & 1; }
 // qmeta: req_head 0-3 | req_cnt 4-8 | res_head 9-12 | res_cnt 13-17
-__host__ __device__ __forceinline__ uint32_t pack_qmeta(uint32_t rqh, uint32_t rqc, uint32_t rsh,
-                                                        uint32_t rsc) {
+constexpr uint32_t QM_REQ = 0x1FFu, QM_RES = 0xFu << 9 | 0x1Fu << 13;   // a queue's head and count
+__host__ __device__ __forceinline__ constexpr uint32_t pack_qmeta(uint32_t rqh, uint32_t rqc,
+                                                                  uint32_t rsh, uint32_t rsc) {
   return rqh | rqc << 4 | rsh << 9 | rsc << 13;
 }
+__host__ __device__ __forceinline__ constexpr uint32_t qm_req_head(uint32_t qm) { return qm & 15; }
+__host__ __device__ __forceinline__ constexpr uint32_t qm_req_cnt(uint32_t qm) { return (qm >> 4) & 31; }
+__host__ __device__ __forceinline__ constexpr uint32_t qm_res_head(uint32_t qm) { return (qm >> 9) & 15; }
+__host__ __device__ __forceinline__ constexpr uint32_t qm_res_cnt(uint32_t qm) { return (qm >> 13) & 31; }
+
+namespace packed_check {
+constexpr uint32_t fl = pack_flags(3, 15, 15, 7, 1, 1), qm = pack_qmeta(15, 31, 15, 31);
+static_assert(fl_role(fl) == 3 && fl_vf(fl) == 15 && fl_lid(fl) == 15 && fl_fault(fl) == 7 &&
+                  fl_seq(fl) == 1 && fl_lsp(fl) == 1,
+              "every flags reader returns the field it was packed with");
+static_assert(fl == (FL_ROLE | FL_VF | FL_LID | FL_FAULT | FL_SEQ | FL_LSP) && !(fl & FL_DRAW),
+              "the masks cover the fields and FL_DRAW lies outside them");
+static_assert(qm_req_head(qm) == 15 && qm_req_cnt(qm) == 31 && qm_res_head(qm) == 15 &&
+                  qm_res_cnt(qm) == 31 && qm == (QM_REQ | QM_RES) && !(QM_REQ & QM_RES),
+              "every qmeta reader returns the field it was packed with");
+}  // namespace packed_check
 
 // One queue's registers: ring head, count, head arrival (INF when empty), tail arrival.
 struct QueueR {

@@ -22,6 +22,7 @@ hipError_t configure_kernels();
 // violations_kernel.hip
 hipError_t launch_viol_clear(const DevSim& S, hipStream_t st);
 size_t viol_scratch_words(uint32_t C);
+const uint32_t* viol_total_ptr(const uint32_t* scratch, uint32_t C);
 hipError_t launch_viol_query(const DevSim& S, uint32_t kinds, uint64_t t_lo, uint64_t t_hi,
                              uint32_t* scratch, void* out, uint32_t cap, hipStream_t st);
 // census_kernel.hip
@@ -43,6 +44,10 @@ static thread_local char g_err[512];
 static int fail(int code, const char* fmt, const char* detail = "") {
   snprintf(g_err, sizeof g_err, fmt, detail);
   return code;
+}
+
+static int unusable() {
+  return fail(-EIO, "a previous step failed part-way; the handle is unusable");
 }
 
 #define HIP_OK(expr)                                                               \
@@ -106,15 +111,14 @@ struct Shard {
   // client-sets at followers. Any host write of state or of the clock ends it (0).
   uint32_t storm_until;
   bool storm_ran = false;              // a storm-kernel launch has run (raftsim_diag_storm_bails)
-  // raft_viol_read: the compaction's chunk counts (violations_kernel.hip), the events around its
-  // kernels (raftsim_diag_viol_ms) and their device time at the last query
+  // The device-side queries. qev0 / qev1: the events around a query's kernels. raft_viol_read: the
+  // compaction's scratch (violations_kernel.hip) and the device time of the last query
+  // (raftsim_diag_viol_ms). raft_census_read / raft_census_select (census_kernel.hip): their
+  // scratch, made by the first query, and the last query's device time (raftsim_diag_census_ms).
+  hipEvent_t qev0, qev1;
   uint32_t* vscratch;
-  hipEvent_t vev0, vev1;
   double viol_ms;
-  // raft_census_read / raft_census_select (census_kernel.hip): their scratch and the events around
-  // their kernels (raftsim_diag_census_ms), made by the first query; the last query's device time
   unsigned long long* cscratch;
-  hipEvent_t cev0, cev1;
   double census_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
@@ -199,10 +203,8 @@ static void sh_destroy(Shard* s) {
   if (s->bail_host) (void)hipHostFree(s->bail_host);
   if (s->ev_start) (void)hipEventDestroy(s->ev_start);
   if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
-  if (s->vev0) (void)hipEventDestroy(s->vev0);
-  if (s->vev1) (void)hipEventDestroy(s->vev1);
-  if (s->cev0) (void)hipEventDestroy(s->cev0);
-  if (s->cev1) (void)hipEventDestroy(s->cev1);
+  if (s->qev0) (void)hipEventDestroy(s->qev0);
+  if (s->qev1) (void)hipEventDestroy(s->qev1);
   for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -330,8 +332,8 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
   if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_start)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_stop)) != hipSuccess ||
-      (e = hipEventCreate(&s->vev0)) != hipSuccess ||
-      (e = hipEventCreate(&s->vev1)) != hipSuccess ||
+      (e = hipEventCreate(&s->qev0)) != hipSuccess ||
+      (e = hipEventCreate(&s->qev1)) != hipSuccess ||
       (e = hipMemsetAsync(d.hot, 0, (size_t)s->C * d.HB * 4, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.qbuf, 0, NN * 2 * s->Q * 32, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.arena, 0, (NN * (size_t)s->A + rs::ARENA_PAD_SLOTS) * 8, s->stream)) != hipSuccess ||
@@ -506,7 +508,7 @@ static uint32_t* hot_word(Shard* s, uint32_t cluster, uint32_t id, uint32_t f) {
   return s->d.hot + (size_t)cluster * s->d.HB + rs::HOT_CW + (size_t)f * s->N + (id - 1);
 }
 static uint32_t* cl_words(Shard* s, uint32_t cluster) {
-  return s->d.hot + (size_t)cluster * s->d.HB + rs::hot_cl_off(s->N);
+  return s->d.hot + (size_t)cluster * s->d.HB;
 }
 
 static int check_node(Shard* s, uint32_t cluster, uint32_t id) {
@@ -540,8 +542,8 @@ static int sh_read_nodes(Shard* s, uint32_t c0, uint32_t nc, raft_node_t* out) {
     raft_node_t& r = out[i];
     memset(&r, 0, sizeof r);
     const uint32_t fl = f(rs::HF_FLAGS), mk = f(rs::HF_MASKS), qm = f(rs::HF_QMETA);
-    r.role = fl & 3; r.voted_for = (fl >> 2) & 15; r.leader_id = (fl >> 6) & 15;
-    r.fault = (fl >> 10) & 7; r.entries_is_seq = (fl >> 13) & 1; r.ls_present = (fl >> 14) & 1;
+    r.role = rs::fl_role(fl); r.voted_for = rs::fl_vf(fl); r.leader_id = rs::fl_lid(fl);
+    r.fault = rs::fl_fault(fl); r.entries_is_seq = rs::fl_seq(fl); r.ls_present = rs::fl_lsp(fl);
     r.votes = mk & 0xFFFF; r.ls_keys = mk >> 16;
     r.current_term = f(rs::HF_TERM); r.commit_index = f(rs::HF_COMMIT);
     r.log_len = f(rs::HF_LEN); r.deadline = f(rs::HF_DEADLINE);
@@ -555,7 +557,7 @@ static int sh_read_nodes(Shard* s, uint32_t c0, uint32_t nc, raft_node_t* out) {
     }
     r.last_led_term = f(rs::hf_led(N));
     r.arena_base = f(rs::hf_abase(N)); r.arena_frontier = f(rs::hf_afront(N));
-    r.req_count = (qm >> 4) & 31; r.res_count = (qm >> 13) & 31;
+    r.req_count = rs::qm_req_cnt(qm); r.res_count = rs::qm_res_cnt(qm);
     r.trace_hash = (uint64_t)f(rs::HF_TRACE_HI) << 32 | f(rs::HF_TRACE_LO);
     r.commit_count = cc[i];
   }
@@ -626,8 +628,8 @@ static int sh_read_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t which
                           qpitch(s, which), sizeof(raft_msg_t), s->Q,
                           hipMemcpyDeviceToHost, s->stream));
   HIP_OK(hipStreamSynchronize(s->stream));
-  const uint32_t head = which ? (qm >> 9) & 15 : qm & 15;
-  const uint32_t cnt = which ? (qm >> 13) & 31 : (qm >> 4) & 31;
+  const uint32_t head = which ? rs::qm_res_head(qm) : rs::qm_req_head(qm);
+  const uint32_t cnt = which ? rs::qm_res_cnt(qm) : rs::qm_req_cnt(qm);
   for (uint32_t i = 0; i < cnt && i < cap && out; ++i) out[i] = slots[(head + i) % s->Q];
   return (int)cnt;
 }
@@ -656,8 +658,8 @@ static int sh_write_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t whic
   uint32_t qm = 0;
   HIP_OK(d2h(s, &qm, hot_word(s, cluster, id, rs::HF_QMETA), 1));
   HIP_OK(hipStreamSynchronize(s->stream));
-  if (which) qm = (qm & ~(0xFu << 9 | 0x1Fu << 13)) | count << 13;
-  else qm = (qm & ~0x1FFu) | count << 4;
+  if (which) qm = (qm & ~rs::QM_RES) | rs::pack_qmeta(0, 0, 0, count);
+  else qm = (qm & ~rs::QM_REQ) | rs::pack_qmeta(0, count, 0, 0);
   const uint32_t harr = count ? in[0].arrival : rs::INF, tail = count ? in[count - 1].arrival : 0;
   HIP_OK(hipMemcpy2DAsync(qring(s, gi, which), qpitch(s, which), slots.data(),
                           sizeof(raft_msg_t), sizeof(raft_msg_t), s->Q, hipMemcpyHostToDevice,
@@ -921,7 +923,7 @@ static bool horizon_ok(const raft_sim_config_t& c, uint64_t tick, uint32_t n) {
 
 int raft_sim_step_async(raft_sim_t* r, uint32_t n_ticks) {
   if (!r) return fail(-EINVAL, "null sim");
-  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  if (r->poisoned) return unusable();
   if (!horizon_ok(r->cfg, r->tick, n_ticks))
     return fail(-ERANGE, "tick + n_ticks + the longest timer would reach 2^32-1");
   for (Shard* s : r->sh) {
@@ -1101,21 +1103,26 @@ int raft_sim_read_counters(raft_sim_t* r, raft_counters_t* out) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Violation records (include/raftsim.h, "no reference counterpart"): the compaction runs on every
-// shard's stream at once, behind whatever the shard has enqueued; shards are contiguous cluster
-// ranges, so their results concatenated in shard order are sorted, and a record's cluster is
-// rebased from the shard to the handle.
-int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64_t t_hi,
-                       raft_violation_t* out, uint32_t cap) {
-  if (!r) return fail(-EINVAL, "null sim");
-  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
-  if (kinds_mask == 0 || kinds_mask > 7) return fail(-EINVAL, "kinds_mask must be 1..7");
-  if (t_lo > t_hi) return fail(-EINVAL, "t_lo must be <= t_hi");
-  if (cap && !out) return fail(-EINVAL, "null output");
+// The sharded query path of raft_viol_read and raft_census_select: a compaction (compact.hpp) runs
+// on every shard's stream at once, behind whatever the shard has enqueued; shards are contiguous
+// cluster ranges, so their results concatenated in shard order are sorted, and a record's cluster
+// is rebased from the shard to the handle. Returns the handle's total, with the first `cap`
+// records in out.
+//   name      the calling function, for error messages
+//   prepare   (Shard*) -> int: what the shard needs before its first query; may fail
+//   enqueue   (Shard*, Rec* dout, uint32_t dcap, const uint32_t** dtotal) -> hipError_t: launch the
+//             query into the device buffer dout of dcap records; *dtotal: where its total will stand
+//   ms        the shard's field for the device time of the query's kernels
+template <class Rec, class Prepare, class Enqueue>
+static int64_t sharded_query(raft_sim_t* r, uint32_t cap, Rec* out, const char* name,
+                             Prepare prepare, Enqueue enqueue, double Shard::*ms) {
   const size_t G = r->sh.size();
   // shard d can contribute min(cap, its clusters) records at most; freed on every path below
-  std::vector<raft_violation_t*> dout(G, nullptr);
+  std::vector<Rec*> dout(G, nullptr);
   std::vector<uint32_t> dcap(G, 0), total(G, 0);
+  char herr[64], merr[64];
+  snprintf(herr, sizeof herr, "HIP error in %s: %%s", name);
+  snprintf(merr, sizeof merr, "hipMalloc failed in %s: %%s", name);
   int rc = 0;
   auto step = [&](hipError_t e, const char* what) {
     if (!rc && e != hipSuccess) rc = fail(-EIO, what, hipGetErrorString(e));
@@ -1124,36 +1131,30 @@ int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64
   for (size_t d = 0; d < G && !rc; ++d) {
     Shard* s = r->sh[d];
     dcap[d] = std::min(cap, s->C);
-    if (!step(hipSetDevice(s->cfg.device), "HIP error in raft_viol_read: %s")) break;
-    if (dcap[d] && !step(hipMalloc(reinterpret_cast<void**>(&dout[d]),
-                                   (size_t)dcap[d] * sizeof(raft_violation_t)),
-                         "hipMalloc failed in raft_viol_read: %s"))
+    if (!step(hipSetDevice(s->cfg.device), herr) || (rc = prepare(s))) break;
+    if (dcap[d] && !step(hipMalloc(reinterpret_cast<void**>(&dout[d]), (size_t)dcap[d] * sizeof(Rec)),
+                         merr))
       break;
-    if (step(hipEventRecord(s->vev0, s->stream), "HIP error in raft_viol_read: %s") &&
-        step(rs::launch_viol_query(s->d, kinds_mask, t_lo, t_hi, s->vscratch, dout[d], dcap[d],
-                                   s->stream),
-             "HIP error in raft_viol_read: %s") &&
-        step(hipEventRecord(s->vev1, s->stream), "HIP error in raft_viol_read: %s"))
-      step(d2h(s, &total[d], s->vscratch + rs::viol_scratch_words(s->C) - 1, 1),
-           "HIP error in raft_viol_read: %s");
+    const uint32_t* dtotal = nullptr;
+    if (step(hipEventRecord(s->qev0, s->stream), herr) &&
+        step(enqueue(s, dout[d], dcap[d], &dtotal), herr) &&
+        step(hipEventRecord(s->qev1, s->stream), herr))
+      step(d2h(s, &total[d], dtotal, 1), herr);
   }
   int64_t sum = 0;
   for (size_t d = 0; d < G && !rc; ++d) {
     Shard* s = r->sh[d];
-    if (!step(hipSetDevice(s->cfg.device), "HIP error in raft_viol_read: %s") ||
-        !step(hipStreamSynchronize(s->stream), "HIP error in raft_viol_read: %s"))
+    if (!step(hipSetDevice(s->cfg.device), herr) || !step(hipStreamSynchronize(s->stream), herr))
       break;
-    float ms = 0;
-    if (!step(hipEventElapsedTime(&ms, s->vev0, s->vev1), "HIP error in raft_viol_read: %s")) break;
-    s->viol_ms = ms;
+    float t = 0;
+    if (!step(hipEventElapsedTime(&t, s->qev0, s->qev1), herr)) break;
+    s->*ms = t;
     // the handle's first `cap` matches: what is left of cap after the shards before this one
     const uint32_t left = (uint64_t)sum < cap ? cap - (uint32_t)sum : 0u;
     const uint32_t n = std::min(std::min(total[d], dcap[d]), left);
     if (n) {
-      raft_violation_t* dst = out + sum;
-      if (!step(hipMemcpy(dst, dout[d], (size_t)n * sizeof(raft_violation_t),
-                          hipMemcpyDeviceToHost),
-                "HIP error in raft_viol_read: %s"))
+      Rec* dst = out + sum;
+      if (!step(hipMemcpy(dst, dout[d], (size_t)n * sizeof(Rec), hipMemcpyDeviceToHost), herr))
         break;
       for (uint32_t i = 0; i < n; ++i) dst[i].cluster += r->lo[d];
     }
@@ -1169,9 +1170,27 @@ int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64
   return rc ? rc : sum;
 }
 
+// Violation records (include/raftsim.h, "no reference counterpart").
+int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64_t t_hi,
+                       raft_violation_t* out, uint32_t cap) {
+  if (!r) return fail(-EINVAL, "null sim");
+  if (r->poisoned) return unusable();
+  if (kinds_mask == 0 || kinds_mask > 7) return fail(-EINVAL, "kinds_mask must be 1..7");
+  if (t_lo > t_hi) return fail(-EINVAL, "t_lo must be <= t_hi");
+  if (cap && !out) return fail(-EINVAL, "null output");
+  return sharded_query(
+      r, cap, out, "raft_viol_read", [](Shard*) { return 0; },
+      [&](Shard* s, raft_violation_t* dout, uint32_t dcap, const uint32_t** dtotal) {
+        *dtotal = rs::viol_total_ptr(s->vscratch, s->C);
+        return rs::launch_viol_query(s->d, kinds_mask, t_lo, t_hi, s->vscratch, dout, dcap,
+                                     s->stream);
+      },
+      &Shard::viol_ms);
+}
+
 int raft_viol_clear(raft_sim_t* r) {
   if (!r) return fail(-EINVAL, "null sim");
-  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  if (r->poisoned) return unusable();
   for (Shard* s : r->sh) {
     HIP_OK(hipSetDevice(s->cfg.device));
     HIP_OK(rs::launch_viol_clear(s->d, s->stream));
@@ -1198,20 +1217,15 @@ extern "C" int raftsim_diag_viol_ms(raft_sim_t* r, double* ms) {
 // kernels over the hot blocks on every shard's stream at once, behind whatever the shard has
 // enqueued. They touch neither the state nor the host's bookkeeping of it (storm_until,
 // keys_written, the steady path choice), so a certificate stays and the next step runs as it would
-// have. The census is folded over the shards on the host; selections concatenate in shard order,
-// rebased to the handle, as raft_viol_read's do.
+// have. The census is folded over the shards on the host; selections go through sharded_query.
 static int census_prepare(Shard* s) {
   if (s->cscratch) return 0;
-  hipError_t e;
-  if ((!s->cev0 && (e = hipEventCreate(&s->cev0)) != hipSuccess) ||
-      (!s->cev1 && (e = hipEventCreate(&s->cev1)) != hipSuccess))
-    return fail(-EIO, "HIP error in the census: %s", hipGetErrorString(e));
   return dalloc(s, &s->cscratch, rs::census_scratch_words(s->C, s->N));   // freed by sh_destroy
 }
 
 int raft_census_read(raft_sim_t* r, raft_census_t* out) {
   if (!r || !out) return fail(-EINVAL, "null argument");
-  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
+  if (r->poisoned) return unusable();
   const size_t G = r->sh.size();
   std::vector<raft_census_t> part(G);
   int rc = 0;
@@ -1224,9 +1238,9 @@ int raft_census_read(raft_sim_t* r, raft_census_t* out) {
     Shard* s = r->sh[d];
     if (!step(hipSetDevice(s->cfg.device)) || (rc = census_prepare(s))) break;
     ++started;
-    step(hipEventRecord(s->cev0, s->stream)) &&
+    step(hipEventRecord(s->qev0, s->stream)) &&
         step(rs::launch_census(s->d, s->cscratch, s->stream)) &&
-        step(hipEventRecord(s->cev1, s->stream)) &&
+        step(hipEventRecord(s->qev1, s->stream)) &&
         step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]),
                  (const unsigned long long*)s->cscratch + rs::census_result_word(s->C, s->N),
                  sizeof(raft_census_t) / 8));
@@ -1238,7 +1252,7 @@ int raft_census_read(raft_sim_t* r, raft_census_t* out) {
     float ms = 0;
     step(hipSetDevice(s->cfg.device));
     step(hipStreamSynchronize(s->stream));
-    if (rc || !step(hipEventElapsedTime(&ms, s->cev0, s->cev1))) continue;
+    if (rc || !step(hipEventElapsedTime(&ms, s->qev0, s->qev1))) continue;
     s->census_ms = ms;
     rs::census_combine(out, &part[d]);
   }
@@ -1252,61 +1266,15 @@ int64_t raft_census_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, 
     return fail(-EINVAL, "class masks must be <= RAFT_CLS_ALL (511)");
   if (all_mask & none_mask) return fail(-EINVAL, "all_mask and none_mask share a class");
   if (cap && !out) return fail(-EINVAL, "null output");
-  if (r->poisoned) return fail(-EIO, "a previous step failed part-way; the handle is unusable");
-  const size_t G = r->sh.size();
-  // shard d can contribute min(cap, its clusters) records at most; freed on every path below
-  std::vector<raft_cluster_state_t*> dout(G, nullptr);
-  std::vector<uint32_t> dcap(G, 0), total(G, 0);
-  int rc = 0;
-  auto step = [&](hipError_t e, const char* what) {
-    if (!rc && e != hipSuccess) rc = fail(-EIO, what, hipGetErrorString(e));
-    return !rc;
-  };
-  const char* const herr = "HIP error in raft_census_select: %s";
-  for (size_t d = 0; d < G && !rc; ++d) {
-    Shard* s = r->sh[d];
-    dcap[d] = std::min(cap, s->C);
-    if (!step(hipSetDevice(s->cfg.device), herr) || (rc = census_prepare(s))) break;
-    if (dcap[d] && !step(hipMalloc(reinterpret_cast<void**>(&dout[d]),
-                                   (size_t)dcap[d] * sizeof(raft_cluster_state_t)),
-                         "hipMalloc failed in raft_census_select: %s"))
-      break;
-    if (step(hipEventRecord(s->cev0, s->stream), herr) &&
-        step(rs::launch_census_select(s->d, any_mask, all_mask, none_mask, s->cscratch, dout[d],
-                                      dcap[d], s->stream),
-             herr) &&
-        step(hipEventRecord(s->cev1, s->stream), herr))
-      step(d2h(s, &total[d], rs::census_total_ptr(s->cscratch, s->C, s->N), 1), herr);
-  }
-  int64_t sum = 0;
-  for (size_t d = 0; d < G && !rc; ++d) {
-    Shard* s = r->sh[d];
-    if (!step(hipSetDevice(s->cfg.device), herr) || !step(hipStreamSynchronize(s->stream), herr))
-      break;
-    float ms = 0;
-    if (!step(hipEventElapsedTime(&ms, s->cev0, s->cev1), herr)) break;
-    s->census_ms = ms;
-    // the handle's first `cap` matches: what is left of cap after the shards before this one
-    const uint32_t left = (uint64_t)sum < cap ? cap - (uint32_t)sum : 0u;
-    const uint32_t n = std::min(std::min(total[d], dcap[d]), left);
-    if (n) {
-      raft_cluster_state_t* dst = out + sum;
-      if (!step(hipMemcpy(dst, dout[d], (size_t)n * sizeof(raft_cluster_state_t),
-                          hipMemcpyDeviceToHost),
-                herr))
-        break;
-      for (uint32_t i = 0; i < n; ++i) dst[i].cluster += r->lo[d];
-    }
-    sum += total[d];
-  }
-  for (size_t d = 0; d < G; ++d) {
-    if (!rc && !dout[d]) continue;
-    (void)hipSetDevice(r->sh[d]->cfg.device);
-    // after an error a shard's kernels may still write dout[d] and its copy total[d]
-    if (rc && r->sh[d]->stream) (void)hipStreamSynchronize(r->sh[d]->stream);
-    if (dout[d]) (void)hipFree(dout[d]);
-  }
-  return rc ? rc : sum;
+  if (r->poisoned) return unusable();
+  return sharded_query(
+      r, cap, out, "raft_census_select", census_prepare,
+      [&](Shard* s, raft_cluster_state_t* dout, uint32_t dcap, const uint32_t** dtotal) {
+        *dtotal = rs::census_total_ptr(s->cscratch, s->C, s->N);
+        return rs::launch_census_select(s->d, any_mask, all_mask, none_mask, s->cscratch, dout,
+                                        dcap, s->stream);
+      },
+      &Shard::census_ms);
 }
 
 // Diagnostic (not part of include/raftsim.h): device time of the last raft_census_read's or

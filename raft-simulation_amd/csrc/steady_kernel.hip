@@ -203,7 +203,7 @@ template <int N>
 __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t t0, uint32_t nt) {
   static_assert(N >= 2 && N <= 5, "follower masks and the response queue fit four followers");
   constexpr int F = N - 1;
-  constexpr uint32_t HB = hot_block_words(N), CLW = hot_cl_off(N);
+  constexpr uint32_t HB = hot_block_words(N);
   // the words read: the cluster's (checker hwm) and every node field up to the leader-state rows
   // (device.hpp: words 0-122 at N = 5, four lines) -- the leader's rows are picked from them once
   // its id is known, with no second round trip. The image holds whole lines of the block.
@@ -211,7 +211,6 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   constexpr int NW4 = (NWORDS + 3) / 4;
   constexpr int IMGC = (int)(HB / 4) < IMG_SLOTS ? (int)(HB / 4) : IMG_SLOTS;   // chunks staged
   static_assert(NW4 <= IMGC && IMGC % 8 == 0, "the image holds the words read, in whole lines");
-  static_assert(CLW == 0, "the cluster words lead the block");
   __shared__ uint32_t bl_c[LANE_WG], bl_t[LANE_WG];   // per wave: bailed cluster, tick it stopped before
   extern __shared__ __attribute__((aligned(16))) uint32_t dsm[];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -289,7 +288,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t Lc = 0, nlc = 0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const bool lead = (w[HOT_CW + HF_FLAGS * N + k] & 3) == RAFT_LEADER;
+    const bool lead = fl_role(w[HOT_CW + HF_FLAGS * N + k]) == RAFT_LEADER;
     Lc = lead ? (uint32_t)k : Lc;
     nlc += lead;
   }
@@ -343,19 +342,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     fx.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
     fx.qmask = fx.rmask = 0; fx.resA = INF; fx.fpend = allF; fx.nhb = fx.nae = fx.nar = 0;
     const uint32_t Lqm = lpick(HF_QMETA);
-    const uint32_t rsc = (Lqm >> 13) & 31;
+    const uint32_t rsc = qm_res_cnt(Lqm);
     uint32_t need = 0;
 #pragma unroll
     for (int j = 0; j < F; ++j) {
       fx.fdl[j] = lfol(HF_DEADLINE, j);
       fx.ftr[j] = (uint64_t)lfol(HF_TRACE_HI, j) << 32 | lfol(HF_TRACE_LO, j);
       const uint32_t qm = lfol(HF_QMETA, j);
-      lean = lean && (lfol(HF_FLAGS, j) & FL_DRAW) && ((qm >> 4) & 31) <= 1 && !((qm >> 13) & 31);
-      need |= (((qm >> 4) & 31) ? 1u : 0u) << j;
+      // (qm >> 4) & 31 is qm_req_cnt(qm), spelled out: through the reader the kernel's code changes
+      lean = lean && (lfol(HF_FLAGS, j) & FL_DRAW) && ((qm >> 4) & 31) <= 1 && !qm_res_cnt(qm);
+      need |= (qm_req_cnt(qm) ? 1u : 0u) << j;
       fx.qA[j] = INF; fx.qT[j] = fx.qa[j] = fx.qb[j] = 0;
       fx.rT[j] = fx.rA[j] = fx.rB[j] = fx.rH[j] = 0;
     }
-    lean = lean && !((Lqm >> 4) & 31) && rsc <= (uint32_t)F && !(need && rsc) &&
+    lean = lean && !qm_req_cnt(Lqm) && rsc <= (uint32_t)F && !(need && rsc) &&
            (need == 0 || need == allF);
     lth0 = fx.Ldl;
     if (need) {                                     // the append-entries in flight
@@ -497,7 +497,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     // election cut by the launch's end, a state that only looks like init-node -- is bailed.
     {
       auto ifield = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
-      bool pat = active && w[0] == 0 && S.Q >= 2u * F && S.el_base >= P && S.hb >= 2 * d + F;
+      bool pat = active && w[CL_HWM_IDX] == 0 && S.Q >= 2u * F && S.el_base >= P && S.hb >= 2 * d + F;
       const uint32_t T = ifield(HF_TERM, 0);
 #pragma unroll
       for (int k = 0; k < N; ++k) {
@@ -713,10 +713,10 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       const uint32_t f = nfl[k];
-      const bool lead = (f & 3) == RAFT_LEADER;
+      const bool lead = fl_role(f) == RAFT_LEADER;
       L = lead ? (uint32_t)k : L;
       nlead += lead;
-      badn |= ((f >> 10) & 7) | (lead != (((f >> 14) & 1) != 0)) | (lead && (f & FL_DRAW));
+      badn |= fl_fault(f) | (lead != (fl_lsp(f) != 0)) | (lead && (f & FL_DRAW));
     }
     bool bad = !active || nlead != 1 || badn != 0 || S.Q < (uint32_t)F;
     const uint32_t Lid = L + 1;
@@ -781,13 +781,13 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       nx0[j] = nx[j];
       mt0[j] = mt[j];
     }
-    const bool ackbad = Llen > w[CLW];          // a success response would be checker work (P4)
+    const bool ackbad = Llen > w[CL_HWM_IDX];          // a success response would be checker work (P4)
     const uint32_t Lkeys = Lmk >> 16;
     // heartbeats need full leader-state, no LazySeq log and commit within the log
     // (append-entries-rpc's IOOBE/NPE/CCE checks, core.clj:56-67): constant over the launch
     bad = bad || (Lkeys & (((1u << (N + 1)) - 1) & ~1u & ~(1u << Lid))) !=
                      (((1u << (N + 1)) - 1) & ~1u & ~(1u << Lid)) ||
-          ((Lfl >> 13) & 1) || Lcommit > Llen;
+          (Lfl & FL_SEQ) || Lcommit > Llen;
 
 #ifdef RS_WAVELOG
     asm volatile("" ::"v"(Ltr), "v"(fdl[0]), "v"(nx[0]));
@@ -803,15 +803,15 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     }
     if (!bad) {
       const uint32_t Lqm = pick<N>(nqm, L);
-      bad = (Lqm >> 4) & 31;                                   // the leader's REQ queue is empty
-      const uint32_t rsh = (Lqm >> 9) & 15, rsc = (Lqm >> 13) & 31;
+      bad = qm_req_cnt(Lqm);                                   // the leader's REQ queue is empty
+      const uint32_t rsh = qm_res_head(Lqm), rsc = qm_res_cnt(Lqm);
       uint32_t need = 0, rqh[F];
 #pragma unroll
       for (int j = 0; j < F; ++j) {
         const uint32_t qm = fsel(nqm, j);
-        const uint32_t rqc = (qm >> 4) & 31;
-        rqh[j] = qm & 15;
-        bad = bad || rqc > 1 || ((qm >> 13) & 31) != 0;       // <= 1 request, no responses
+        const uint32_t rqc = qm_req_cnt(qm);
+        rqh[j] = qm_req_head(qm);
+        bad = bad || rqc > 1 || qm_res_cnt(qm) != 0;       // <= 1 request, no responses
         need |= (uint32_t)(rqc != 0) << j;
       }
       bad = bad || rsc > (uint32_t)F;
@@ -910,7 +910,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
       for (int j = 0; j < F; ++j)
         ok = ok && fterm[j] == Lterm &&
-             (ffl[j] & (3u | 15u << 2 | 15u << 6 | 1u << 13)) == (RAFT_FOLLWER | Lid << 6) &&
+             (ffl[j] & FL_FOLLOW) == pack_flags(RAFT_FOLLWER, 0, Lid, 0, 0, 0) &&
              fcommit[j] == flen[j] && (fmk[j] & 0xFFFFu) == 0 && nx[j] == 0 &&
              mt[j] == (int32_t)Lcommit;
       return ok;
@@ -1140,11 +1140,11 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           if ((fa >> j) & 1) {
             const uint32_t mterm = qT[j], rterm = fterm[j];
             const bool ok = mterm >= fterm[j];
-            const uint32_t nfl2 = ok ? (ffl[j] & ~(3u | 15u << 2 | 15u << 6 | 1u << 13)) |
-                                           RAFT_FOLLWER | Lid << 6
+            const uint32_t nfl2 = ok ? (ffl[j] & ~FL_FOLLOW) |
+                                           pack_flags(RAFT_FOLLWER, 0, Lid, 0, 0, 0)
                                      : ffl[j];
             const uint32_t nterm = ok ? mterm : fterm[j];
-            ftr[j] = trace_event(ftr[j], ta, RAFT_MSG_APPEND_ENTRIES, Lid, mterm, nfl2 & 3, nterm, 0);
+            ftr[j] = trace_event(ftr[j], ta, RAFT_MSG_APPEND_ENTRIES, Lid, mterm, fl_role(nfl2), nterm, 0);
             if (ok) {
               fcommit[j] = flen[j];                            // apply-entries! (nothing applied)
               fmk[j] &= 0xFFFF0000u;
@@ -1319,7 +1319,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       }
       // the steady certificate for the next launch: the cluster stays at its fixed point
       const uint32_t cn = fp || (full && at_fixed_point_state()) ? (CERT_MAGIC | L) : 0u;
-      *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) = make_uint4(w[4], w[5], w[6], cn);
+      *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) = make_uint4(w[CL_CERT - 3], w[CL_CERT - 2], w[CL_CERT - 1], cn);
       dl |= (uint32_t)(cn != w[CL_CERT]);
       // the leader's rows (node L): next / match of peer fk(j) + 1
       if (!wfp) {

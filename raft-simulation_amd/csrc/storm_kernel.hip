@@ -54,21 +54,23 @@ storm_lane_kernel(DevSim S, uint32_t t0, uint32_t nt,
   // and a node's deadline after the launch follows from its last event (redrawn at the end), so
   // neither is held per event: 12 words per node.
   constexpr uint32_t AM = (1u << 28) - 1;
-  uint32_t cnext = hc[3], ccount = hc[4];
+  uint32_t cnext = hc[CL_CLIENT_NEXT], ccount = hc[CL_CLIENT_COUNT];
   uint32_t qn[N], nb[N];
   uint64_t tr[N];
   uint32_t qa[N][QC], qv[N][QC];
-  const uint32_t term = hp[HF_TERM * N], role = hp[HF_FLAGS * N] & 3;
+  const uint32_t term = hp[HF_TERM * N], role = fl_role(hp[HF_FLAGS * N]);
   bool ok = active && hc[CL_CERT] == 0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     const uint32_t fl = hp[HF_FLAGS * N + k], qm = hp[HF_QMETA * N + k];
     tr[k] = (uint64_t)hp[HF_TRACE_HI * N + k] << 32 | hp[HF_TRACE_LO * N + k];
+    // qm_req_cnt(qm) and, below, qm_res_cnt(qm), spelled out: through the readers the kernel's
+    // code changes
     qn[k] = (qm >> 4) & 31;
     nb[k] = t0;
     // a follower without a leader id, not halted, no owed draw, no responses, no timer inside the
     // launch; the cluster's common term and role
-    ok = ok && (fl & ~(15u << 2)) == role && role != RAFT_LEADER && role != RAFT_CANDIDATE &&
+    ok = ok && (fl & ~FL_VF) == role && role != RAFT_LEADER && role != RAFT_CANDIDATE &&
          hp[HF_TERM * N + k] == term && ((qm >> 13) & 31) == 0 && qn[k] <= QL &&
          hp[HF_DEADLINE * N + k] >= tend;
 #pragma unroll
@@ -220,8 +222,8 @@ storm_lane_kernel(DevSim S, uint32_t t0, uint32_t nt,
         }
       }
     }
-    hc[3] = cnext;
-    hc[4] = ccount;
+    hc[CL_CLIENT_NEXT] = cnext;
+    hc[CL_CLIENT_COUNT] = ccount;
     // the packing key for the next launch, as the general body writes it with client traffic: the
     // busiest clusters first (tick_wave.hpp's write-back; listed clusters get theirs from the rerun)
     if (S.shist) {

@@ -33,13 +33,13 @@ tick_kernel(DevSim S, uint32_t t0, uint32_t nt) {
 __global__ void sched_key_kernel(DevSim S, uint32_t t0) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= S.C) return;
-  uint32_t m = hot_cl(S, c)[3];
+  uint32_t m = hot_cl(S, c)[CL_CLIENT_NEXT];
   for (uint32_t k = 0; k < S.N; ++k) {
     const uint32_t* h = hot_node(S, c, k);
-    if ((h[HF_FLAGS * S.N] >> 10) & 7) continue;
+    if (fl_fault(h[HF_FLAGS * S.N])) continue;
     const uint32_t qm = h[HF_QMETA * S.N];
-    const QueueR rq = {0, (qm >> 4) & 31, h[HF_REQ_ARR * S.N], 0},
-                 rs = {0, (qm >> 13) & 31, h[HF_RES_ARR * S.N], 0};
+    const QueueR rq = {0, qm_req_cnt(qm), h[HF_REQ_ARR * S.N], 0},
+                 rs = {0, qm_res_cnt(qm), h[HF_RES_ARR * S.N], 0};
     m = min(m, sched_key_of(h[HF_DEADLINE * S.N], rq, rs));
   }
   const uint32_t key = sched_bucket(m, t0);
@@ -232,7 +232,7 @@ __global__ void init_kernel(DevSim S) {
     }
     uint32_t* cw = hot_cl(S, c);
     for (int i = 0; i < 8; ++i) cw[i] = 0;
-    cw[3] = first;
+    cw[CL_CLIENT_NEXT] = first;
   }
 }
 
@@ -249,8 +249,8 @@ __global__ void digest_kernel(DevSim S, uint32_t c0, uint32_t nc, unsigned long 
     const uint32_t dl = (fl & FL_DRAW) ? exact_deadline(S.goff + c, k + 1, hw[HF_DEADLINE * N],
                                                         S.el_base, S.el_span, S.key0, S.key1)
                                        : hw[HF_DEADLINE * N];
-    const uint32_t w[12] = {fl & 3, (fl >> 2) & 15, (fl >> 6) & 15, (fl >> 10) & 7,
-                            (fl >> 13) & 1, (fl >> 14) & 1, mk & 0xFFFF, mk >> 16,
+    const uint32_t w[12] = {fl_role(fl), fl_vf(fl), fl_lid(fl), fl_fault(fl),
+                            fl_seq(fl), fl_lsp(fl), mk & 0xFFFF, mk >> 16,
                             hw[HF_TERM * N], hw[HF_COMMIT * N], hw[HF_LEN * N], dl};
     for (int i = 0; i < 12; ++i) h = fnv(h, w[i]);
     for (uint32_t p = 0; p < 2 * N; ++p) h = fnv(h, hw[(HF_NEXT + p) * N]);   // next, then match
@@ -282,7 +282,8 @@ __global__ void digest_kernel(DevSim S, uint32_t c0, uint32_t nc, unsigned long 
         h = fnv(h, e.y);
       }
     }
-    const uint32_t qh[2] = {qm & 15, (qm >> 9) & 15}, qc[2] = {(qm >> 4) & 31, (qm >> 13) & 31};
+    const uint32_t qh[2] = {qm_req_head(qm), qm_res_head(qm)},
+                   qc[2] = {qm_req_cnt(qm), qm_res_cnt(qm)};
     for (int which = 0; which < 2; ++which) {
       h = fnv(h, qc[which]);
       const uint32_t* qb = qslots(S, gi, which);

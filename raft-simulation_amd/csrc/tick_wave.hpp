@@ -550,10 +550,10 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
     const uint32_t g = S.goff + c;
     const int bl0 = (cs < CPW ? cs : 0) * N;     // the cluster's first lane
     const uint32_t A = S.A;
-    constexpr uint32_t HB = hot_block_words(N), CLW = hot_cl_off(N);
+    constexpr uint32_t HB = hot_block_words(N);
     // this node's words in its cluster's block (field f at hp[f * N]) and the cluster's words
     uint32_t* const hp = S.hot + (size_t)c * HB + HOT_CW + k0;
-    uint32_t* const hc = S.hot + (size_t)c * HB + CLW;
+    uint32_t* const hc = S.hot + (size_t)c * HB;
 
     NodeR n = {};
     uint32_t hidx = 0, hterm = 0, hval = 0;   // checker high-water mark (cluster-replicated)
@@ -576,21 +576,23 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
     uint32_t cnext = INF, ccount = 0;         // client-set injection cursor (cluster-replicated)
     if (active) {
       const uint32_t fl = hp[HF_FLAGS * N], mk = hp[HF_MASKS * N], qm = hp[HF_QMETA * N];
-      n.role = fl & 3; n.vf = (fl >> 2) & 15; n.lid = (fl >> 6) & 15; n.fault = (fl >> 10) & 7;
-      n.seq = (fl >> 13) & 1;
-      n.votes = mk & 0xFFFF; n.keys = mk >> 16 | ((fl >> 14) & 1);
+      n.role = fl_role(fl); n.vf = fl_vf(fl); n.lid = fl_lid(fl); n.fault = fl_fault(fl);
+      n.seq = fl_seq(fl);
+      n.votes = mk & 0xFFFF; n.keys = mk >> 16 | fl_lsp(fl);
       n.term = hp[HF_TERM * N]; n.commit = hp[HF_COMMIT * N]; n.len = hp[HF_LEN * N];
       n.deadline = hp[HF_DEADLINE * N];
       if (!SPEC) {                                        // a deferred draw carried over
         if constexpr (REGS) dpend_r = (fl & FL_DRAW) ? 1u : 0u;
         else dpend[lane] = (fl & FL_DRAW) ? 1u : 0u;
       }
-      n.rq.h = qm & 15; n.rq.c = (qm >> 4) & 31; n.rs.h = (qm >> 9) & 15; n.rs.c = (qm >> 13) & 31;
+      n.rq.h = qm_req_head(qm); n.rq.c = qm_req_cnt(qm);
+      n.rs.h = qm_res_head(qm); n.rs.c = qm_res_cnt(qm);
       n.rq.arr = hp[HF_REQ_ARR * N]; n.rs.arr = hp[HF_RES_ARR * N];
       n.rq.tail = hp[HF_REQ_TAIL * N]; n.rs.tail = hp[HF_RES_TAIL * N];
       n.base = hp[hf_abase(N) * N]; n.front = hp[hf_afront(N) * N]; n.led = hp[hf_led(N) * N];
       n.trace = (uint64_t)hp[HF_TRACE_HI * N] << 32 | hp[HF_TRACE_LO * N];
-      hidx = hc[0]; hterm = hc[1]; hval = hc[2]; cnext = hc[3]; ccount = hc[4];
+      hidx = hc[CL_HWM_IDX]; hterm = hc[CL_HWM_TERM]; hval = hc[CL_HWM_VAL];
+      cnext = hc[CL_CLIENT_NEXT]; ccount = hc[CL_CLIENT_COUNT];
       if constexpr (nm_lds_in<N, STORM>()) {   // each lane only touches its own LDS column
   #pragma unroll
         for (int p = 0; p < N; ++p) {
@@ -1986,7 +1988,7 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
       uint32_t cw = c;
       asm volatile("" : "+v"(cw));
       uint32_t* const hp = S.hot + (size_t)cw * HB + HOT_CW + k0;
-      uint32_t* const hc = S.hot + (size_t)cw * HB + CLW;
+      uint32_t* const hc = S.hot + (size_t)cw * HB;
       hp[HF_FLAGS * N] = pack_flags(n.role, n.vf, n.lid, n.fault, n.seq, n.keys & 1u) | owed;
       hp[HF_MASKS * N] = n.votes | (n.keys & ~1u) << 16;
       hp[HF_TERM * N] = n.term; hp[HF_COMMIT * N] = n.commit; hp[HF_LEN * N] = n.len;
@@ -2004,7 +2006,8 @@ __device__ __forceinline__ void tick_wave(const DevSim& S, uint32_t t0, uint32_t
         }
       }
       if (k0 == 0) {
-        hc[0] = hidx; hc[1] = hterm; hc[2] = hval; hc[3] = cnext; hc[4] = ccount;
+        hc[CL_HWM_IDX] = hidx; hc[CL_HWM_TERM] = hterm; hc[CL_HWM_VAL] = hval;
+        hc[CL_CLIENT_NEXT] = cnext; hc[CL_CLIENT_COUNT] = ccount;
         hc[CL_CERT] = 0;                    // the steady certificate no longer holds (device.hpp)
       }
     }

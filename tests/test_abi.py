@@ -48,7 +48,22 @@ def test_library_is_built_from_these_sources():
     assert lib.raftsim_src_hash().decode() == _build.source_hash()
 
 
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
+def test_source_hash_covers_every_included_project_file():
+    """Every project file that a file of KERNEL_SOURCES includes (#include "...") is itself in
+    KERNEL_SOURCES: a header left out could change without the hash, and with it the stale-binary
+    check, noticing."""
+    from raftsim import _build
+
+    listed = {(ROOT / f).resolve() for f in _build.KERNEL_SOURCES}
+    includes = 0
+    for src in sorted(listed):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src.read_text(), re.M):
+            includes += 1
+            assert (src.parent / inc).resolve() in listed, f"{src.name} includes {inc}"
+    assert includes >= 6, "every .hip file includes a project header: the pattern misses them"
+
+
+CSRC =ROOT / "raft-simulation_amd" / "csrc"
 # the compile-time switches csrc/device.hpp declares (diagnostic builds only)
 SWITCHES = ["RS_BURST", "RS_BURST_MIN", "RS_BURST_SKIP", "RS_BURST_DIAG", "RS_WAVELOG"]
 
