@@ -342,11 +342,38 @@ constexpr uint32_t FL_DRAW = 1u << 15;
 // writer of a block clears it: the general tick body's write-back, raft_sim_write_nodes,
 // raft_sim_write_queue and raft_sim_write_clusters (whose reserved words it is; reads return them
 // zeroed), and the init kernel.
+//
+// The strong certificate: CL_CERT = CERT_STRONG | L with the leader's term in cluster word CL_CTERM,
+// both in the 16-B chunk of words 4-7 (one store). Written by the steady kernel's certified path
+// for every cluster it writes back, it promises everything the plain certificate does, and:
+//   - the cluster is on the fixed point's period-P schedule (P = 2d + F - 1 + hb): at the tick the
+//     launch ended no round is in progress, or the round's append-entries are in flight to every
+//     follower, or its responses are queued at the leader exactly as the launch's end cut them;
+//   - every follower's draw is owed (FL_DRAW), its flags are FL_FOLLOW-shaped with the leader's
+//     id, the leader's flags are the leader role, and every node's term is word CL_CTERM;
+//   - every word of the block past word 31 that the certified path used to read is a function of
+//     the first line (Ldl: the leader's deadline, rsc: its QMETA response count, j0 = F - rsc):
+//     append-entries in flight (followers' QMETA request count 1): REQ_ARR = REQ_TAIL =
+//     Ldl - hb + d for every follower; responses cut (rsc > 0): the leader's RES_ARR = RES_TAIL =
+//     Ldl - hb - (j0 ? j0 - 1 : -2d) (Ldl is the heartbeat's tick + hb until the first response
+//     is taken, then the last taken response's tick + hb); every other REQ_ARR / RES_ARR is INF
+//     and every other tail 0.
+// The next steady launch then runs such a cluster from the first line of its block alone
+// (steady_kernel.hip). The later lines still hold the true values: whatever else reads a block
+// (digest, census, violations, node and queue reads, the general tick body) never looks at
+// the certificate. Both forms live in CL_CERT, so every writer that clears the plain one clears
+// the strong one; CL_CTERM means nothing without CERT_STRONG and is left stale. Nothing else
+// stores to a certified block: the storm kernel skips blocks with CL_CERT != 0, and the digest,
+// census and violations kernels only read. Like CL_CERT, CL_CTERM is outside the digest (words
+// 0-4), returned as zero by raft_sim_read_clusters, zeroed by raft_sim_write_clusters, and read
+// by no other kernel.
 // The cluster's other words are raft_cluster_t's: the checker's high-water mark (index, term, val)
-// and the client's next injection tick and count. Words 5 and 6 are unused.
+// and the client's next injection tick and count. Word 5 is unused.
 enum ClusterWord : uint32_t { CL_HWM_IDX, CL_HWM_TERM, CL_HWM_VAL, CL_CLIENT_NEXT, CL_CLIENT_COUNT };
+constexpr uint32_t CL_CTERM = 6;
 constexpr uint32_t CL_CERT = 7;
 constexpr uint32_t CERT_MAGIC = 0x5EAD0000u;
+constexpr uint32_t CERT_STRONG = 0x57A90000u;
 __host__ __device__ __forceinline__ uint32_t exact_deadline(uint32_t g, uint32_t id, uint32_t lb,
                                                             uint32_t el_base, uint32_t el_span,
                                                             uint32_t k0, uint32_t k1) {

@@ -52,17 +52,25 @@ __device__ __forceinline__ uint32_t msel(bool a, uint32_t x, uint32_t y) {
 // four 128-B lines at N >= 4) in LDS: loads and stores then move whole lines, eight lines per wave
 // instruction, where a lane reading its own cluster's block straight into registers touches 64
 // lines per instruction (one per lane, the texture path's rate) -- the load phase's cost.
-// Two halves: lines 0-1 of every cluster, then lines 2-3 (loaded only when some cluster of the
-// wave has no steady certificate, device.hpp). In a half, chunk i of the wave's cluster l sits in
-// slot i ^ (l & 15) of l's 256-B row: the LDS-DMA loads (global_load_lds: lane-linear destination)
-// take the swizzle on their source addresses, and a lane reading chunk i of its own cluster, or
-// writing it back, meets no bank conflict (the 16 lanes of a ds_read_b128 group have distinct
-// l & 15).
-constexpr int IMG_SLOTS = 32;                               // chunks per cluster, both halves
-constexpr uint32_t IMG_HALF = 64 * 16 * 16;                 // 16 KiB: 64 clusters x 16 chunks
+// Three parts: line 0 of every cluster, line 1 of every cluster (loaded only when some cluster of
+// the wave has no strong certificate, device.hpp), then lines 2-3 (only when some cluster has no
+// certificate at all). The LDS-DMA loads (global_load_lds: lane-linear destination, 1 KiB per wave
+// instruction) take the swizzles on their source addresses.
+// Lines 0 and 1: chunk i of line ln of the wave's cluster l sits in slot (i & 7) ^ img_sw(l) of
+// l's 128-B row of that line's 8-KiB part, so one DMA instruction fills eight clusters' rows. A
+// lane reading chunk i of its own cluster meets no bank conflict (the 16 lanes of a ds_read_b128
+// group have distinct l & 15: the row's half of the 256 B of banks is l & 1, and (l & 1,
+// img_sw(l)) is distinct for distinct l & 15), nor does it writing the chunk back (ds_write_b128:
+// eight consecutive lanes over 128 B of banks, img_sw distinct), nor do the line stores' reads.
+// Lines 2-3: chunk i sits in slot (i & 15) ^ (l & 15) of l's 256-B row.
+constexpr int IMG_SLOTS = 32;                               // chunks per cluster, all parts
+constexpr uint32_t IMG_LINE = 64 * 8 * 16;                  // 8 KiB: 64 clusters x 8 chunks
+constexpr uint32_t IMG_HALF = 2 * IMG_LINE;                 // 16 KiB: lines 0-1, or lines 2-3
 constexpr uint32_t IMG_WAVE = 2 * IMG_HALF;                 // 32 KiB per wave
+__device__ __forceinline__ uint32_t img_sw(uint32_t l) { return (l ^ (l >> 3)) & 7u; }
 __device__ __forceinline__ uint32_t img_off(uint32_t l, uint32_t i) {
-  return (i >> 4) * IMG_HALF + l * 256u + 16u * ((i & 15u) ^ (l & 15u));
+  return i < 16 ? (i >> 3) * IMG_LINE + l * 128u + 16u * ((i & 7u) ^ img_sw(l))
+                : IMG_HALF + l * 256u + 16u * ((i & 15u) ^ (l & 15u));
 }
 template <typename T>
 __device__ __forceinline__ T* lds_at(char* img, uint32_t off) {
@@ -258,52 +266,45 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #endif
 
   // ------------------------------------------- load: the wave's blocks into its image (LDS-DMA)
-  // half h (lines 2h, 2h + 1): wave instruction j takes clusters 4j .. 4j + 3, 16 slots each
-  auto load_half = [&](int h) {
+  // line ln (0 or 1): wave instruction j takes clusters 8j .. 8j + 7, 8 slots each
+  auto load_line = [&](int ln) {
+    const uint32_t p = lane & 7;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t cc = 8 * j + (lane >> 3);
+      const uint32_t i = 8 * ln + (p ^ img_sw(cc));
+      const uint32_t cg = min(cbase + cc, S.C - 1);  // past the shard's end: any block, unused
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(S.hot + (size_t)cg * HB + 4 * i),
+          (__attribute__((address_space(3))) void*)(img + ln * IMG_LINE + j * 1024), 16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's own LDS-DMA writes landed
+  };
+  // lines 2-3: wave instruction j takes clusters 4j .. 4j + 3, 16 slots each
+  auto load_half1 = [&]() {
     const uint32_t p = lane & 15;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t cc = 4 * j + (lane >> 4);
-      const uint32_t i = 16 * h + (p ^ (cc & 15u));
-      const uint32_t cg = min(cbase + cc, S.C - 1);  // past the shard's end: any block, unused
+      const uint32_t i = 16 + (p ^ (cc & 15u));
+      const uint32_t cg = min(cbase + cc, S.C - 1);
       if (i < (uint32_t)IMGC)
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(S.hot + (size_t)cg * HB + 4 * i),
-            (__attribute__((address_space(3))) void*)(img + h * IMG_HALF + j * 1024), 16, 0, 0);
+            (__attribute__((address_space(3))) void*)(img + IMG_HALF + j * 1024), 16, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's own LDS-DMA writes landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
+  static_assert(IMGC >= 16, "lines 0 and 1 are whole in every block");
   uint32_t w[NW4 * 4];
 #pragma unroll
   for (int i = 0; i < NW4 * 4; ++i) w[i] = 0;
-  load_half(0);
+  load_line(0);
 #pragma unroll
-  for (int i = 0; i < (NW4 < 16 ? NW4 : 16); ++i) {
+  for (int i = 0; i < (NW4 < 8 ? NW4 : 8); ++i) {
     const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
     w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
   }
-  // The steady certificate (device.hpp): a cluster the last steady launch left at its fixed point
-  // with leader L needs only the first two lines. The rest is loaded when some cluster of the wave
-  // lacks one; otherwise those words read as the fixed point's (zero).
-  uint32_t Lc = 0, nlc = 0;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const bool lead = fl_role(w[HOT_CW + HF_FLAGS * N + k]) == RAFT_LEADER;
-    Lc = lead ? (uint32_t)k : Lc;
-    nlc += lead;
-  }
-  static_assert(HOT_CW + (HF_FLAGS + 1) * N <= 64, "the flags are in the first two lines");
-  const bool cert = active && nlc == 1 && w[CL_CERT] == (CERT_MAGIC | Lc);
-  const bool full = IMGC > 16 && __builtin_amdgcn_ballot_w64(active && !cert) != 0;   // uniform
-  if (full) {
-    load_half(1);
-#pragma unroll
-    for (int i = 16; i < NW4; ++i) {
-      const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
-      w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
-    }
-  }
-  const bool vouched = cert && !full;         // its lines past the second are the fixed point's
   const uint32_t tend = t0 + nt, d = S.dmin;
   const uint32_t P = 2 * d + F - 1 + S.hb, allF = (1u << F) - 1;
   uint32_t dl = 0, nhb = 0, nae = 0, nar = 0;  // lines of the block changed; events run
@@ -311,20 +312,143 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t el_to = 0;                          // its timeouts (two candidates: a tie)
 #ifdef RS_WAVELOG
   uint64_t wl_x1 = 0, wl_x2 = 0, wl_x3 = 0, wl_lend = 0;
+  asm volatile("" ::"v"(w[CL_CERT]), "v"(w[HOT_CW]));
+  wl_loop = wall_clock64();                   // line 0 loaded
 #endif
 
-  // ------------------------------------------- the certified path
-  // A wave whose every cluster is vouched for by its certificate (device.hpp), on the fixed
+  // ------------------------------------------- the certified path from line 0 alone
+  // A wave whose every cluster holds a strong certificate (device.hpp) runs the whole launch from
+  // the first line of its blocks: the leader's id and term are in the certificate's chunk, the
+  // deadlines, trace hashes and QMETA words are in line 0 (every N), and whatever else the
+  // certified path below reads from the later lines (flags, the term, the head arrivals of the
+  // messages in flight) is what the certificate says it is. What picks the round in progress at
+  // t0 is tested on first-line words: the followers' QMETA (no request, or one each), the leader's
+  // (its response count) and the deadlines against t0 (set_tick moves the clock under a
+  // certificate). A cluster that fails a test sends its wave to the two-line path below.
+  static_assert(HOT_CW + (HF_QMETA + 1) * N <= 32 && HF_DEADLINE < HF_QMETA &&
+                    HF_TRACE_LO < HF_QMETA && HF_TRACE_HI < HF_QMETA && CL_CTERM < HOT_CW,
+                "every word the line-0 path reads is in line 0; REQ_ARR, RES_ARR, the flags and "
+                "the term are derived (device.hpp)");
+  FixedPoint<N> fx;
+  uint32_t lmid = 0, lth0 = 0;
+  const bool cfg_ok = S.el_base >= P && S.hb >= 2 * d + F && S.Q >= (uint32_t)F;
+  bool strong = active && cfg_ok && (w[CL_CERT] & 0xFFFF0000u) == CERT_STRONG &&
+                (w[CL_CERT] & 0xFFFFu) < (uint32_t)N;
+  {
+    const uint32_t L = w[CL_CERT] & 0xFFFFu;
+    auto lw = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
+    auto lpick = [&](int f) {                       // field f of the leader
+      uint32_t v = 0;
+#pragma unroll
+      for (int k = 0; k < N; ++k) v |= lw(f, k) & (0u - (uint32_t)(L == (uint32_t)k));
+      return v;
+    };
+    auto lfol = [&](int f, int j) {                 // field f of follower slot j
+      const uint32_t m = 0u - (uint32_t)((uint32_t)j >= L);
+      return (lw(f, j + 1) & m) | (lw(f, j) & ~m);
+    };
+    fx.L = L; fx.Lid = L + 1; fx.Lterm = w[CL_CTERM]; fx.Lcommit = 0;
+    fx.Ldl = lpick(HF_DEADLINE);
+    fx.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
+    fx.qmask = fx.rmask = 0; fx.resA = INF; fx.fpend = allF; fx.nhb = fx.nae = fx.nar = 0;
+    const uint32_t Lqm = lpick(HF_QMETA), rsc = qm_res_cnt(Lqm);
+    // a certified block's rings have their heads at slot 0: the followers' QMETA words are all
+    // "no message" or all "one request", the leader's is its response count
+    const uint32_t qm0 = lfol(HF_QMETA, 0);
+    const bool need = qm0 != 0;
+    strong = strong && (qm0 & ~pack_qmeta(0, 1, 0, 0)) == 0 && Lqm == pack_qmeta(0, 0, 0, rsc) &&
+             rsc <= (uint32_t)F && !(need && rsc);
+#pragma unroll
+    for (int j = 0; j < F; ++j) {
+      fx.fdl[j] = lfol(HF_DEADLINE, j);
+      fx.ftr[j] = (uint64_t)lfol(HF_TRACE_HI, j) << 32 | lfol(HF_TRACE_LO, j);
+      if (j) strong = strong && lfol(HF_QMETA, j) == qm0;
+      fx.qA[j] = INF; fx.qT[j] = fx.qa[j] = fx.qb[j] = 0;
+      fx.rT[j] = fx.rA[j] = fx.rB[j] = fx.rH[j] = 0;
+    }
+    lth0 = fx.Ldl;
+    if (need) {                                     // the append-entries in flight
+      lmid = 1;
+      lth0 = fx.Ldl - S.hb;
+      const uint32_t ta = lth0 + d;
+      strong = strong && fx.Ldl >= S.hb && ta >= t0;
+#pragma unroll
+      for (int j = 0; j < F; ++j) {
+        fx.qA[j] = ta; fx.qT[j] = fx.Lterm;
+      }
+      fx.qmask = allF;
+    } else if (rsc) {                               // the responses the last launch's end cut
+      lmid = 2;
+      // the leader's deadline is the round's heartbeat + hb until it takes a response, then that
+      // response's tick (th + 2d + j0 - 1 for the j0-th) + hb
+      const uint32_t j0 = (uint32_t)F - rsc, back = S.hb + (j0 ? 2 * d + j0 - 1 : 0u);
+      lth0 = fx.Ldl - back;
+      const uint32_t ra = lth0 + 2 * d;
+      const int64_t cut = (int64_t)t0 - (int64_t)ra;
+      strong = strong && fx.Ldl >= back &&
+               (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut);
+      fx.rmask = allF & ~((1u << j0) - 1);
+      fx.resA = ra;
+#pragma unroll
+      for (int j = 0; j < F; ++j) {
+        fx.rT[j] = fx.Lterm; fx.rH[j] = 1;
+      }
+    } else {
+      strong = strong && fx.Ldl >= t0;
+    }
+    const uint32_t nxt = min((lmid == 2 ? lth0 + P : lth0) + d, tend);   // the next AE (or end)
+#pragma unroll
+    for (int j = 0; j < F; ++j) strong = strong && fx.fdl[j] >= nxt;
+  }
+  const bool line0_wave = !__builtin_amdgcn_ballot_w64(active && !strong);   // uniform
+
+  // The steady certificate (device.hpp): a cluster the last steady launch left at its fixed point
+  // with leader L needs only the first two lines. The rest is loaded when some cluster of the wave
+  // lacks one; otherwise those words read as the fixed point's (zero).
+  uint32_t Lc = 0;
+  bool cert = false, full = false;
+  if (!line0_wave) {
+    load_line(1);
+#pragma unroll
+    for (int i = 8; i < (NW4 < 16 ? NW4 : 16); ++i) {
+      const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
+      w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
+    }
+    uint32_t nlc = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const bool lead = fl_role(w[HOT_CW + HF_FLAGS * N + k]) == RAFT_LEADER;
+      Lc = lead ? (uint32_t)k : Lc;
+      nlc += lead;
+    }
+    static_assert(HOT_CW + (HF_FLAGS + 1) * N <= 64, "the flags are in the first two lines");
+    cert = active && nlc == 1 &&
+           (w[CL_CERT] == (CERT_MAGIC | Lc) || w[CL_CERT] == (CERT_STRONG | Lc));
+    full = IMGC > 16 && __builtin_amdgcn_ballot_w64(active && !cert) != 0;   // uniform
+    if (full) {
+      load_half1();
+#pragma unroll
+      for (int i = 16; i < NW4; ++i) {
+        const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
+        w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
+      }
+    }
+  }
+  const bool vouched = cert && !full;         // its lines past the second are the fixed point's
+
+  // ------------------------------------------- the certified path from two lines
+  // A wave whose every cluster is vouched for by a certificate (device.hpp), on the fixed
   // point's period-P schedule (its round in progress at t0: none, the append-entries in flight, or
   // the responses the last launch's end cut) and with its followers' draws owed (FL_DRAW) runs the
   // whole launch from the first two lines of its blocks: the rest of that round, then
   // FixedPoint::rounds. Queued messages are not read: a certified cluster's are the fixed point's
   // (whatever else writes a ring clears the certificate), and so are its leader's commit (0) and
-  // the rest of its state. Any other wave takes the general path below.
-  FixedPoint<N> fx;
-  uint32_t lmid = 0, lth0 = 0;
-  bool lean = vouched && S.el_base >= P && S.hb >= 2 * d + F && S.Q >= (uint32_t)F;
-  {
+  // the rest of its state. It leaves every cluster with a strong certificate: the next launch
+  // takes the line-0 path above. Any other wave takes the general path below.
+  bool lean = strong;
+  if (!line0_wave) {
+    lean = vouched && cfg_ok;
+    lmid = 0;
     const uint32_t L = Lc;
     auto lw = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
     auto lpick = [&](int f) {                       // field f of the leader
@@ -392,6 +516,10 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   const bool lean_wave = !__builtin_amdgcn_ballot_w64(active && !lean);     // uniform
   bool wb = false;
   if (lean_wave) {
+#ifdef RS_WAVELOG
+    asm volatile("" ::"v"(fx.Ltr), "v"(fx.fdl[0]), "v"(fx.ftr[0]), "v"(lth0));
+    wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
+#endif
     if (active) {
       bool whole = true;                      // the round in progress finished in this launch
       if (lmid == 1) {
@@ -404,6 +532,10 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       }
       if (whole) fx.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base);
       nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
+#ifdef RS_WAVELOG
+      asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
+      wl_x3 = wall_clock64();                 // the rounds done
+#endif
       // fields DEADLINE .. RES_TAIL of every node back into the image (the rest is unchanged)
       const uint32_t L = fx.L;
       uint32_t v[HF_FLAGS][N];
@@ -427,17 +559,37 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         v[HF_REQ_TAIL][k] = isL ? 0u : (fq ? fqa : 0u);
         v[HF_RES_TAIL][k] = isL ? (fx.rmask ? fx.resA : 0u) : 0u;
       }
-      auto in = [](int q) { return q >= (int)HOT_CW && q < (int)(HOT_CW + HF_FLAGS * N); };
+      // (HOT_CW + HF_FLAGS * N is a multiple of 4 for every N: these chunks hold no other word)
+      static_assert((HOT_CW + HF_FLAGS * N) % 4 == 0 && HOT_CW % 4 == 0, "whole chunks");
+      constexpr int CH_END = (int)(HOT_CW + HF_FLAGS * N) / 4;
       auto val = [&](int q) { return v[(q - HOT_CW) / N][(q - HOT_CW) % N]; };
+      auto chunk = [&](int i) {
+        return make_uint4(val(4 * i), val(4 * i + 1), val(4 * i + 2), val(4 * i + 3));
+      };
+      // A line-0 wave has no old line 1 to compare with: line 0 goes through the image, and the
+      // chunks past it (the head and tail arrivals of messages in flight) change only for a
+      // cluster with a round in progress at the launch's start or its end -- stored below.
 #pragma unroll
-      for (int i = (int)HOT_CW / 4; i < (int)(HOT_CW + HF_FLAGS * N + 3) / 4; ++i) {
-        const int q = 4 * i;
-        const uint4 x = make_uint4(in(q) ? val(q) : w[q], in(q + 1) ? val(q + 1) : w[q + 1],
-                                   in(q + 2) ? val(q + 2) : w[q + 2],
-                                   in(q + 3) ? val(q + 3) : w[q + 3]);
-        *lds_at<uint4>(img, img_off(lane, i)) = x;
-        dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3])
-              << (i / 8);
+      for (int i = (int)HOT_CW / 4; i < CH_END; ++i) {
+        if (i < 8 || !line0_wave) {                          // wave-uniform
+          const int q = 4 * i;
+          const uint4 x = chunk(i);
+          *lds_at<uint4>(img, img_off(lane, i)) = x;
+          dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3])
+                << (i / 8);
+        }
+      }
+      if (!line0_wave) {
+        // the strong certificate and the leader's term (device.hpp), one chunk
+        const uint32_t cn = CERT_STRONG | L;
+        *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) =
+            make_uint4(w[CL_CERT - 3], w[CL_CERT - 2], fx.Lterm, cn);
+        static_assert(CL_CTERM == CL_CERT - 1 && CL_CERT % 4 == 3, "one chunk");
+        dl |= (uint32_t)(cn != w[CL_CERT] || fx.Lterm != w[CL_CTERM]);
+      } else if (CH_END > 8 && (lmid || fx.qmask || fx.rmask)) {   // rare
+        uint4* const bp = reinterpret_cast<uint4*>(S.hot + (size_t)c * HB);
+#pragma unroll
+        for (int i = 8; i < CH_END; ++i) bp[i] = chunk(i);
       }
     }
     // messages in flight at the launch's end back to the rings, heads at slot 0 (rare)
@@ -464,7 +616,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       }
     }
 #ifdef RS_WAVELOG
-    wl_loop = wl_x1 = wl_x2 = wl_x3 = wl_lend = wall_clock64();
+    wl_lend = wall_clock64();                   // the image and the rings written
 #endif
   } else {
 #ifdef RS_WAVELOG

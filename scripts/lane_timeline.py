@@ -17,9 +17,11 @@ sim = Backend(sys.argv[1], "raft_sim_", n_clusters=C, nodes=5, seed=42)
 for _ in range(LAUNCHES):
     sim.step(10000)
 waves = 2 * C // 12 + 1000
-buf = (ctypes.c_uint32 * (waves * 32))()
+# raftsim_diag_wavelog copies 192 B per wave of its count (the general kernel's record size); the
+# steady kernel's records are 128 B apart from the buffer's start
+buf = (ctypes.c_uint32 * (waves * 48))()
 n = sim._lib.raftsim_diag_wavelog(sim._h, buf, waves)
-a = np.frombuffer(buf, dtype=np.uint32).reshape(-1, 32)[:n].astype(np.int64)
+a = np.frombuffer(buf, dtype=np.uint32)[:n * 48 // 32 * 32].reshape(-1, 32).astype(np.int64)
 a = a[(a[:, 0] | a[:, 1]) != 0]
 start = a[:, 0] | (a[:, 1] << 32)
 end = a[:, 2] | (a[:, 3] << 32)
