@@ -27,6 +27,7 @@
 // draw per follower per launch instead of one per round, with identical results.
 #include <hip/hip_ext.h>
 
+#include "fixed_point_affine.hpp"
 #include "tick_wave.hpp"
 
 namespace rs {
@@ -103,6 +104,52 @@ __host__ __device__ constexpr uint64_t trace_geo() {
   return s;
 }
 
+// fixed_point_affine.hpp restates the hash's constants without this project's headers
+static_assert(fpa::M == TRACE_M && fpa::M2 == TRACE_M2 && fpa::ROLE_LEADER == RAFT_LEADER &&
+                  fpa::ROLE_FOLLWER == RAFT_FOLLWER &&
+                  fpa::EV_APPEND_ENTRIES == RAFT_MSG_APPEND_ENTRIES &&
+                  fpa::EV_APPEND_RESPONSE == RAFT_MSG_APPEND_RESPONSE,
+              "the affine step's hash is the trace hash");
+
+// The affine maps (fixed_point_affine.hpp) of the two counts of whole rounds a launch holds for a
+// cluster on the schedule: its first heartbeat th of the launch is in [t0, t0 + P), so it runs
+// K1 = K(th = t0) whole rounds or one fewer. A wave builds both on the scalar unit while its
+// line-0 load is in flight and keeps them in LDS (scalar registers are what the kernel lacks, and
+// 36 vector registers held from the kernel's top to the rounds cost the small-N kernels a wave of
+// occupancy); a lane reads the set of its own K, five 16-B reads.
+struct alignas(16) SetWords {                         // fpa::Set's maps, K rounds; K1 beside them
+  uint64_t la, lx, ly, lz, fa, fx, fy, fz;
+  uint32_t ls, fs, K, K1;
+  __device__ __forceinline__ fpa::Half lead() const { return fpa::Half{la, lx, ly, lz, ls}; }
+  __device__ __forceinline__ fpa::Half fol() const { return fpa::Half{fa, fx, fy, fz, fs}; }
+};
+struct BandSets {
+  SetWords k[2];                                      // k[1] is K1 rounds, k[0] is K1 - 1
+};
+__device__ __forceinline__ uint32_t vreg(uint32_t s) {   // a uniform value, from the scalar unit
+  uint32_t v;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+  return v;
+}
+__device__ __forceinline__ uint64_t vreg(uint64_t s) {
+  return (uint64_t)vreg((uint32_t)(s >> 32)) << 32 | vreg((uint32_t)s);
+}
+__device__ __forceinline__ SetWords vreg(const fpa::Set& c, uint32_t K1) {
+  return SetWords{vreg(c.lead.a), vreg(c.lead.x), vreg(c.lead.y), vreg(c.lead.z),
+                  vreg(c.fol.a),  vreg(c.fol.x),  vreg(c.fol.y),  vreg(c.fol.z),
+                  vreg(c.lead.s), vreg(c.fol.s),  vreg(c.K),      vreg(K1)};
+}
+// The sets of a launch of nt ticks into *out. Uniform arguments: scalar code, moved to vector
+// registers (the stores' data) by instructions the compiler keeps in program order.
+template <int F>
+__device__ __forceinline__ void band_sets(uint32_t nt, uint32_t d, uint32_t hb, BandSets* out) {
+  const uint32_t P = fpa::period(F, d, hb), last = 2 * d + F - 1;
+  const uint32_t K1 = nt > last ? (nt - last - 1) / P + 1 : 0;
+  const fpa::Set lo = fpa::build<F>(d, hb, K1 ? K1 - 1 : 0), hi = fpa::step<F>(lo, d, hb);
+  out->k[0] = vreg(lo, K1);
+  out->k[1] = vreg(hi, K1);
+}
+
 // A cluster at its fixed point, lane-resident: every follower took the leader's append-entries
 // (flags, votes, term and commit are what another one sets again), every response succeeded (next /
 // match / keys as another one sets them), the log is empty (a heartbeat ships nothing). With the
@@ -157,30 +204,46 @@ struct FixedPoint {
   // that end before it as trace hashes alone, then the one it cuts (heartbeat, append-entries and
   // responses up to tend - 1; what is left stays queued as the general body leaves it). Every next
   // event of the cluster is then at or after tend.
+  //
+  // The K whole rounds are one affine step of each hash (fixed_point_affine.hpp) when K is one of
+  // the two counts the wave's sets hold, as it is for every cluster on the schedule; when some lane
+  // here has another K (set_tick moved the clock, an election ended mid-launch, ...) all of them
+  // take the loop over rounds instead.
   __device__ __forceinline__ void rounds(uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
-                                         uint32_t el_base) {
+                                         uint32_t el_base, const BandSets& bs) {
     const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1;
     const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
     const uint32_t tk = th + K * P;
     if (K) {
-      // The trace hash is polynomial (device.hpp): a round's F + 1 leader events take the
-      // leader's hash h to h * M2^(F+1) + a, with a the Horner sum of the events' terms, and a
-      // round P ticks later adds P * M * (1 + M2 + ... + M2^F) to a; a follower's one event per
-      // round takes h to h * M2 + c, and c grows by P * M. One multiply-add per hash per round.
-      uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, Lterm, 0);
+      const uint32_t K1 = bs.k[0].K1;
+      const bool top = K == K1;
+      if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
+        const SetWords sw = bs.k[top];                            // the lane's own set (K rounds)
+        const fpa::Half cl = sw.lead(), cf = sw.fol();
+        Ltr = fpa::apply_leader<F>(cl, Ltr, th, Lterm, L);
+        const uint64_t add = fpa::follower_addend<F>(cf, th, Lterm, L);
 #pragma unroll
-      for (int j = 0; j < F; ++j)
-        a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, fk(j) + 1, Lterm,
-                                      RAFT_LEADER, Lterm, 0);
-      const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
-      const uint64_t df = (uint64_t)P * TRACE_M;
-      uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, Lid, Lterm, RAFT_FOLLWER, Lterm, 0);
-      for (uint32_t r = 0; r < K; ++r) {
-        Ltr = Ltr * trace_pow<F + 1>() + a;
-        a += da;
+        for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * cf.a + add;
+      } else {
+        // The trace hash is polynomial (device.hpp): a round's F + 1 leader events take the
+        // leader's hash h to h * M2^(F+1) + a, with a the Horner sum of the events' terms, and a
+        // round P ticks later adds P * M * (1 + M2 + ... + M2^F) to a; a follower's one event per
+        // round takes h to h * M2 + c, and c grows by P * M. One multiply-add per hash per round.
+        uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, Lterm, 0);
 #pragma unroll
-        for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * TRACE_M2 + cf;
-        cf += df;
+        for (int j = 0; j < F; ++j)
+          a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, fk(j) + 1, Lterm,
+                                        RAFT_LEADER, Lterm, 0);
+        const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
+        const uint64_t df = (uint64_t)P * TRACE_M;
+        uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, Lid, Lterm, RAFT_FOLLWER, Lterm, 0);
+        for (uint32_t r = 0; r < K; ++r) {
+          Ltr = Ltr * trace_pow<F + 1>() + a;
+          a += da;
+#pragma unroll
+          for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * TRACE_M2 + cf;
+          cf += df;
+        }
       }
 #pragma unroll
       for (int j = 0; j < F; ++j) fdl[j] = tk - P + d + el_base;   // + the owed draw
@@ -220,6 +283,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   constexpr int IMGC = (int)(HB / 4) < IMG_SLOTS ? (int)(HB / 4) : IMG_SLOTS;   // chunks staged
   static_assert(NW4 <= IMGC && IMGC % 8 == 0, "the image holds the words read, in whole lines");
   __shared__ uint32_t bl_c[LANE_WG], bl_t[LANE_WG];   // per wave: bailed cluster, tick it stopped before
+  __shared__ BandSets bs_keep[LANE_WG / 64];          // per wave: the launch's affine sets
   extern __shared__ __attribute__((aligned(16))) uint32_t dsm[];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     // the previous steady launch's bail count (complete: that launch has ended) to the host, which
@@ -267,7 +331,10 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 
   // ------------------------------------------- load: the wave's blocks into its image (LDS-DMA)
   // line ln (0 or 1): wave instruction j takes clusters 8j .. 8j + 7, 8 slots each
-  auto load_line = [&](int ln) {
+  auto load_wait = [&]() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's own LDS-DMA writes landed
+  };
+  auto load_line = [&](int ln, bool wait) {
     const uint32_t p = lane & 7;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -278,7 +345,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           (const __attribute__((address_space(1))) void*)(S.hot + (size_t)cg * HB + 4 * i),
           (__attribute__((address_space(3))) void*)(img + ln * IMG_LINE + j * 1024), 16, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's own LDS-DMA writes landed
+    if (wait) load_wait();
   };
   // lines 2-3: wave instruction j takes clusters 4j .. 4j + 3, 16 slots each
   auto load_half1 = [&]() {
@@ -299,7 +366,15 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t w[NW4 * 4];
 #pragma unroll
   for (int i = 0; i < NW4 * 4; ++i) w[i] = 0;
-  load_line(0);
+  load_line(0, false);
+  // The launch's affine sets, while the load is in flight: nt passes through an empty statement
+  // after the load's instructions, so nothing of the build is scheduled before them, and the
+  // sets' moves out of the scalar registers (band_sets) stand before the wait.
+  uint32_t nt_s = nt;
+  asm volatile("" : "+s"(nt_s));
+  const BandSets& bs = bs_keep[wave];
+  band_sets<F>(nt_s, S.dmin, S.hb, &bs_keep[wave]);
+  load_wait();
 #pragma unroll
   for (int i = 0; i < (NW4 < 8 ? NW4 : 8); ++i) {
     const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
@@ -408,7 +483,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t Lc = 0;
   bool cert = false, full = false;
   if (!line0_wave) {
-    load_line(1);
+    load_line(1, true);
 #pragma unroll
     for (int i = 8; i < (NW4 < 16 ? NW4 : 16); ++i) {
       const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
@@ -530,7 +605,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         fx.responses(lth0, tend, d, S.hb);
         whole = !fx.rmask;
       }
-      if (whole) fx.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base);
+      if (whole) fx.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base, bs);
       nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
 #ifdef RS_WAVELOG
       asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
@@ -1085,7 +1160,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         x.qA[j] = qA[j]; x.qT[j] = qT[j]; x.qa[j] = qa[j]; x.qb[j] = qb[j];
         x.rT[j] = rT[j]; x.rA[j] = rA[j]; x.rB[j] = rB[j]; x.rH[j] = rH[j];
       }
-      x.rounds(th, tend, d, S.hb, S.el_base);
+      x.rounds(th, tend, d, S.hb, S.el_base, bs);
       Ltr = x.Ltr; Ldl = x.Ldl; fpend = x.fpend; qmask = x.qmask; rmask = x.rmask; resA = x.resA;
       nhb = x.nhb; nae = x.nae; nar = x.nar;
 #pragma unroll

@@ -20,6 +20,7 @@ KERNEL_SOURCES = ["raft-simulation_amd/csrc/tick_kernel.hip",
                   "raft-simulation_amd/csrc/census_kernel.hip",
                   "raft-simulation_amd/csrc/tick_wave.hpp", "raft-simulation_amd/csrc/device.hpp",
                   "raft-simulation_amd/csrc/compact.hpp",
+                  "raft-simulation_amd/csrc/fixed_point_affine.hpp",
                   "raft-simulation_amd/csrc/raftsim.hip", "include/raftsim.h"]
 # "diag": a diagnostic build (csrc/device.hpp's switches, RS_DIAG_BUILD), whatever its sources
 _TAG = re.compile(rb"RAFTSIM_SRC_HASH=([0-9a-f]{16}|unknown|diag)")
