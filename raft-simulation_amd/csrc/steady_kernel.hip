@@ -270,6 +270,105 @@ struct FixedPoint {
   }
 };
 
+// A cluster under a strong certificate (device.hpp), lane-resident in node order: the line-0 body's
+// state. On the fixed point's schedule what FixedPoint keeps per follower slot is one value for all
+// followers -- they take the same append-entries at the same tick with the same term, so they share
+// its arrival, the deadline it re-arms, their QMETA and tails -- and the responses queued at the
+// leader are the last rc slots in slot order, all of the leader's term, successful, with one
+// arrival. Only the trace hashes differ, and a hash needs no slot: every hash takes the followers'
+// step (one addend for all), slot L's is dead and the leader's own (Ltr) replaces it at write-back.
+// Events, ticks and hash terms are FixedPoint's.
+template <int N>
+struct NodeOrder {
+  static constexpr int F = N - 1;
+  uint32_t L, T;                                     // the leader's index; every node's term
+  uint64_t tr[N], Ltr;                               // hashes by node (tr[L] dead); the leader's
+  uint32_t Ldl;
+  bool qin, took;                                    // append-entries in flight; one taken here
+  uint32_t qA, fdl;                                  // their arrival; the deadline the taken one set
+  uint32_t rc, resA;                                 // responses queued (slots F - rc ..), arrival
+  uint32_t nhb, nae, nar;
+
+  __device__ __forceinline__ uint32_t sid(int j) const {   // the id of follower slot j
+    return (uint32_t)j + 1 + ((uint32_t)j >= L ? 1u : 0u);
+  }
+  __device__ __forceinline__ void followers(uint64_t a, uint64_t add) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) tr[k] = tr[k] * a + add;
+  }
+  __device__ __forceinline__ void append_entries(uint32_t ta, uint32_t d, uint32_t el_base) {
+    followers(TRACE_M2, trace_term(ta, RAFT_MSG_APPEND_ENTRIES, L + 1, T, RAFT_FOLLWER, T, 0));
+    took = true;
+    fdl = ta + el_base;                               // + the owed draw
+    qin = false;
+    rc = F;
+    resA = ta + d;
+    nae += F;
+  }
+  __device__ __forceinline__ void responses(uint32_t th, uint32_t tend, uint32_t d, uint32_t hb) {
+#pragma unroll
+    for (int j = 0; j < F; ++j) {
+      const uint32_t tau = th + 2 * d + j;
+      if ((uint32_t)j + rc >= (uint32_t)F && tau < tend) {   // slot j is queued
+        Ltr = trace_event(Ltr, tau, RAFT_MSG_APPEND_RESPONSE, sid(j), T, RAFT_LEADER, T, 0);
+        --rc;
+        Ldl = tau + hb;
+        ++nar;
+      }
+    }
+    if (!rc) resA = INF;
+  }
+  // FixedPoint::rounds on this state
+  __device__ __forceinline__ void rounds(uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
+                                         uint32_t el_base, const BandSets& bs) {
+    const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1;
+    const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
+    const uint32_t tk = th + K * P;
+    if (K) {
+      const uint32_t K1 = bs.k[0].K1;
+      const bool top = K == K1;
+      if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
+        const SetWords sw = bs.k[top];                            // the lane's own set (K rounds)
+        const fpa::Half cl = sw.lead(), cf = sw.fol();
+        Ltr = fpa::apply_leader<F>(cl, Ltr, th, T, L);
+        followers(cf.a, fpa::follower_addend<F>(cf, th, T, L));
+      } else {                                                    // round by round (FixedPoint)
+        uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, T, 0);
+#pragma unroll
+        for (int j = 0; j < F; ++j)
+          a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, sid(j), T,
+                                        RAFT_LEADER, T, 0);
+        const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
+        const uint64_t df = (uint64_t)P * TRACE_M;
+        uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, L + 1, T, RAFT_FOLLWER, T, 0);
+        for (uint32_t r = 0; r < K; ++r) {
+          Ltr = Ltr * trace_pow<F + 1>() + a;
+          a += da;
+          followers(TRACE_M2, cf);
+          cf += df;
+        }
+      }
+      took = true;
+      fdl = tk - P + d + el_base;                 // + the owed draw
+      Ldl = tk;                                   // = the last response + hb
+      nhb += K;
+      nae += F * K;
+      nar += F * K;
+    }
+    if (tk < tend) {                              // the round the launch's end cuts
+      Ltr = trace_event(Ltr, tk, 7, 0, 0, RAFT_LEADER, T, 0);
+      ++nhb;
+      Ldl = tk + hb;
+      qin = true;
+      qA = tk + d;
+      if (tk + d < tend) {                        // the append-entries, then responses in time
+        append_entries(tk + d, d, el_base);
+        responses(tk, tend, d, hb);
+      }
+    }
+  }
+};
+
 template <int N>
 __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t t0, uint32_t nt) {
   static_assert(N >= 2 && N <= 5, "follower masks and the response queue fit four followers");
@@ -285,15 +384,6 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   __shared__ uint32_t bl_c[LANE_WG], bl_t[LANE_WG];   // per wave: bailed cluster, tick it stopped before
   __shared__ BandSets bs_keep[LANE_WG / 64];          // per wave: the launch's affine sets
   extern __shared__ __attribute__((aligned(16))) uint32_t dsm[];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // the previous steady launch's bail count (complete: that launch has ended) to the host, which
-    // picks the next launches' path from it (speed only); that word is this launch's successor's
-    // (host memory is written only when there is something to report: the host zeroes its copy
-    // when it acts on it, and a store there holds the launch's end for a bus round trip)
-    const uint32_t prev = *S.nbail_zero;
-    if (S.bail_report && prev) *S.bail_report = prev;
-    if (prev) *S.nbail_zero = 0;
-  }
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t cbase = blockIdx.x * LANE_WG + wave * 64;      // the wave's clusters, in id order
   const uint32_t c0 = cbase + lane < S.C ? cbase + lane : INF;
@@ -363,10 +453,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   static_assert(IMGC >= 16, "lines 0 and 1 are whole in every block");
-  uint32_t w[NW4 * 4];
-#pragma unroll
-  for (int i = 0; i < NW4 * 4; ++i) w[i] = 0;
+  uint32_t w[NW4 * 4];          // (the words past line 0 are set where a wave leaves the line-0 body)
+  // The arguments the affine sets are built from, fetched with the ones the loads' addresses wait
+  // for: one scalar round trip at the kernel's top, not a second one between the loads' issue and
+  // the build (measured: DESIGN.md, "The line-0 body in node order").
+  asm volatile("" ::"s"(nt), "s"(t0), "s"(S.dmin), "s"(S.hb), "s"(S.el_base));
   load_line(0, false);
+  // The previous steady launch's bail count (complete: that launch has ended) to the host, which
+  // picks the next launches' path from it (speed only); that word is this launch's successor's
+  // (host memory is written only when there is something to report: the host zeroes its copy
+  // when it acts on it, and a store there holds the launch's end for a bus round trip). Read
+  // behind the line-0 loads, in their shadow: nothing here needs it before the kernel ends.
+  const bool reporter = blockIdx.x == 0 && threadIdx.x == 0;
+  uint32_t prev_bails = 0;
+  if (reporter) prev_bails = *S.nbail_zero;
   // The launch's affine sets, while the load is in flight: nt passes through an empty statement
   // after the load's instructions, so nothing of the build is scheduled before them, and the
   // sets' moves out of the scalar registers (band_sets) stand before the wait.
@@ -375,8 +475,13 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   const BandSets& bs = bs_keep[wave];
   band_sets<F>(nt_s, S.dmin, S.hb, &bs_keep[wave]);
   load_wait();
+  if (reporter && prev_bails) {
+    if (S.bail_report) *S.bail_report = prev_bails;
+    *S.nbail_zero = 0;
+  }
+  static_assert(NW4 >= 8, "line 0 is read whole");
 #pragma unroll
-  for (int i = 0; i < (NW4 < 8 ? NW4 : 8); ++i) {
+  for (int i = 0; i < 8; ++i) {
     const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
     w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
   }
@@ -387,6 +492,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t el_to = 0;                          // its timeouts (two candidates: a tie)
 #ifdef RS_WAVELOG
   uint64_t wl_x1 = 0, wl_x2 = 0, wl_x3 = 0, wl_lend = 0;
+  uint32_t wl_cut = 0;
   asm volatile("" ::"v"(w[CL_CERT]), "v"(w[HOT_CW]));
   wl_loop = wall_clock64();                   // line 0 loaded
 #endif
@@ -404,7 +510,9 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
                     HF_TRACE_LO < HF_QMETA && HF_TRACE_HI < HF_QMETA && CL_CTERM < HOT_CW,
                 "every word the line-0 path reads is in line 0; REQ_ARR, RES_ARR, the flags and "
                 "the term are derived (device.hpp)");
-  FixedPoint<N> fx;
+  // The tests and the state are in node order (NodeOrder): nothing is gathered into follower
+  // slots. A follower is "a node that is not L".
+  NodeOrder<N> no;
   uint32_t lmid = 0, lth0 = 0;
   const bool cfg_ok = S.el_base >= P && S.hb >= 2 * d + F && S.Q >= (uint32_t)F;
   bool strong = active && cfg_ok && (w[CL_CERT] & 0xFFFF0000u) == CERT_STRONG &&
@@ -418,64 +526,150 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       for (int k = 0; k < N; ++k) v |= lw(f, k) & (0u - (uint32_t)(L == (uint32_t)k));
       return v;
     };
-    auto lfol = [&](int f, int j) {                 // field f of follower slot j
-      const uint32_t m = 0u - (uint32_t)((uint32_t)j >= L);
-      return (lw(f, j + 1) & m) | (lw(f, j) & ~m);
-    };
-    fx.L = L; fx.Lid = L + 1; fx.Lterm = w[CL_CTERM]; fx.Lcommit = 0;
-    fx.Ldl = lpick(HF_DEADLINE);
-    fx.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
-    fx.qmask = fx.rmask = 0; fx.resA = INF; fx.fpend = allF; fx.nhb = fx.nae = fx.nar = 0;
+    no.L = L; no.T = w[CL_CTERM];
+    no.Ldl = lpick(HF_DEADLINE);
+    no.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
+#pragma unroll
+    for (int k = 0; k < N; ++k) no.tr[k] = (uint64_t)lw(HF_TRACE_HI, k) << 32 | lw(HF_TRACE_LO, k);
+    no.qin = no.took = false; no.qA = no.fdl = 0; no.rc = 0; no.resA = INF;
+    no.nhb = no.nae = no.nar = 0;
     const uint32_t Lqm = lpick(HF_QMETA), rsc = qm_res_cnt(Lqm);
     // a certified block's rings have their heads at slot 0: the followers' QMETA words are all
     // "no message" or all "one request", the leader's is its response count
-    const uint32_t qm0 = lfol(HF_QMETA, 0);
+    const uint32_t qm0 = L ? lw(HF_QMETA, 0) : lw(HF_QMETA, 1);   // the first follower's
     const bool need = qm0 != 0;
     strong = strong && (qm0 & ~pack_qmeta(0, 1, 0, 0)) == 0 && Lqm == pack_qmeta(0, 0, 0, rsc) &&
              rsc <= (uint32_t)F && !(need && rsc);
 #pragma unroll
-    for (int j = 0; j < F; ++j) {
-      fx.fdl[j] = lfol(HF_DEADLINE, j);
-      fx.ftr[j] = (uint64_t)lfol(HF_TRACE_HI, j) << 32 | lfol(HF_TRACE_LO, j);
-      if (j) strong = strong && lfol(HF_QMETA, j) == qm0;
-      fx.qA[j] = INF; fx.qT[j] = fx.qa[j] = fx.qb[j] = 0;
-      fx.rT[j] = fx.rA[j] = fx.rB[j] = fx.rH[j] = 0;
-    }
-    lth0 = fx.Ldl;
+    for (int k = 0; k < N; ++k) strong = strong && (L == (uint32_t)k || lw(HF_QMETA, k) == qm0);
+    lth0 = no.Ldl;
     if (need) {                                     // the append-entries in flight
       lmid = 1;
-      lth0 = fx.Ldl - S.hb;
+      lth0 = no.Ldl - S.hb;
       const uint32_t ta = lth0 + d;
-      strong = strong && fx.Ldl >= S.hb && ta >= t0;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        fx.qA[j] = ta; fx.qT[j] = fx.Lterm;
-      }
-      fx.qmask = allF;
+      strong = strong && no.Ldl >= S.hb && ta >= t0;
+      no.qin = true;
+      no.qA = ta;
     } else if (rsc) {                               // the responses the last launch's end cut
       lmid = 2;
       // the leader's deadline is the round's heartbeat + hb until it takes a response, then that
       // response's tick (th + 2d + j0 - 1 for the j0-th) + hb
       const uint32_t j0 = (uint32_t)F - rsc, back = S.hb + (j0 ? 2 * d + j0 - 1 : 0u);
-      lth0 = fx.Ldl - back;
+      lth0 = no.Ldl - back;
       const uint32_t ra = lth0 + 2 * d;
       const int64_t cut = (int64_t)t0 - (int64_t)ra;
-      strong = strong && fx.Ldl >= back &&
+      strong = strong && no.Ldl >= back &&
                (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut);
-      fx.rmask = allF & ~((1u << j0) - 1);
-      fx.resA = ra;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        fx.rT[j] = fx.Lterm; fx.rH[j] = 1;
-      }
+      no.rc = rsc;
+      no.resA = ra;
     } else {
-      strong = strong && fx.Ldl >= t0;
+      strong = strong && no.Ldl >= t0;
     }
+    // no follower's timer fires before its next append-entries. (The followers' deadlines as
+    // loaded need not be equal: set_tick or an election's exact draw may leave them apart. The
+    // body never reads them again: it writes back the common re-armed one, or the words as loaded.)
     const uint32_t nxt = min((lmid == 2 ? lth0 + P : lth0) + d, tend);   // the next AE (or end)
 #pragma unroll
-    for (int j = 0; j < F; ++j) strong = strong && fx.fdl[j] >= nxt;
+    for (int k = 0; k < N; ++k)
+      strong = strong && (L == (uint32_t)k || lw(HF_DEADLINE, k) >= nxt);
   }
   const bool line0_wave = !__builtin_amdgcn_ballot_w64(active && !strong);   // uniform
+  if (line0_wave) {
+    // ----------------------------------------- the line-0 body: the whole launch in node order
+    // (It stands right behind the decision: its state is dead before the other paths load their
+    // lines. Behind them it stayed live across them and cost the N = 2 kernel a wave of occupancy.)
+#ifdef RS_WAVELOG
+    asm volatile("" ::"v"(no.Ltr), "v"(no.Ldl), "v"(no.tr[0]), "v"(lth0));
+    wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
+#endif
+    if (active) {
+      bool whole = true;                      // the round in progress finished in this launch
+      if (lmid == 1) {
+        if (no.qA < tend) no.append_entries(no.qA, d, S.el_base);
+        else whole = false;
+      }
+      if (lmid && whole) {
+        no.responses(lth0, tend, d, S.hb);
+        whole = !no.rc;
+      }
+      if (whole) no.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base, bs);
+      nhb = no.nhb; nae = no.nae; nar = no.nar;
+#ifdef RS_WAVELOG
+      asm volatile("" ::"v"(no.Ltr), "v"(no.tr[0]), "v"(no.Ldl));
+      wl_x3 = wall_clock64();                 // the rounds done
+#endif
+      // Fields DEADLINE .. RES_TAIL of every node: the leader's value (at k == L) or the followers'
+      // common one. A follower's deadline is the one its last append-entries of this launch set,
+      // or the word as loaded when it took none.
+      const uint32_t fqm = pack_qmeta(0, no.qin ? 1u : 0u, 0, 0), Lqm = pack_qmeta(0, 0, 0, no.rc);
+      const uint32_t fra = no.qin ? no.qA : INF, frt = no.qin ? no.qA : 0u;
+      const uint32_t Lrt = no.rc ? no.resA : 0u;
+      auto val = [&](int q) -> uint32_t {
+        const int f = (q - (int)HOT_CW) / N, k = (q - (int)HOT_CW) % N;
+        const bool isL = no.L == (uint32_t)k;
+        switch (f) {
+          case HF_DEADLINE: return isL ? no.Ldl : no.took ? no.fdl : w[q];
+          case HF_TRACE_LO: return (uint32_t)(isL ? no.Ltr : no.tr[k]);
+          case HF_TRACE_HI: return (uint32_t)((isL ? no.Ltr : no.tr[k]) >> 32);
+          case HF_QMETA: return isL ? Lqm : fqm;
+          case HF_REQ_ARR: return isL ? INF : fra;
+          case HF_RES_ARR: return isL ? no.resA : INF;
+          case HF_REQ_TAIL: return isL ? 0u : frt;
+          default: return isL ? Lrt : 0u;     // HF_RES_TAIL
+        }
+      };
+      static_assert(HF_RES_TAIL + 1 == HF_FLAGS, "the fields written: DEADLINE .. RES_TAIL");
+      static_assert((HOT_CW + HF_FLAGS * N) % 4 == 0 && HOT_CW % 4 == 0, "whole chunks");
+      constexpr int CH_END = (int)(HOT_CW + HF_FLAGS * N) / 4;
+      auto chunk = [&](int i) {
+        return make_uint4(val(4 * i), val(4 * i + 1), val(4 * i + 2), val(4 * i + 3));
+      };
+      // There is no old line 1 to compare with: line 0 goes through the image, and the chunks past
+      // it (the head and tail arrivals of messages in flight) change only for a cluster with a
+      // round in progress at the launch's start or its end -- stored from registers.
+#pragma unroll
+      for (int i = (int)HOT_CW / 4; i < (CH_END < 8 ? CH_END : 8); ++i) {
+        const int q = 4 * i;
+        const uint4 x = chunk(i);
+        *lds_at<uint4>(img, img_off(lane, i)) = x;
+        dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3]);
+      }
+      if (CH_END > 8 && (lmid || no.qin || no.rc)) {   // rare
+        uint4* const bp = reinterpret_cast<uint4*>(S.hot + (size_t)c * HB);
+#pragma unroll
+        for (int i = 8; i < CH_END; ++i) bp[i] = chunk(i);
+      }
+    }
+    // messages in flight at the launch's end back to the rings, heads at slot 0 (rare)
+    if (__builtin_amdgcn_ballot_w64(active && (no.qin || no.rc))) {   // wave-uniform
+      if (active && no.qin) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          if (no.L != (uint32_t)k) {
+            uint4* dp = reinterpret_cast<uint4*>(qslots(S, c * N + k, 0));
+            dp[0] = make_uint4(no.qA, RAFT_MSG_APPEND_ENTRIES | (no.L + 1) << 3, no.T, 0);
+            dp[1] = make_uint4(0, 0, 0, 0);
+          }
+        }
+      }
+      uint4* rp = reinterpret_cast<uint4*>(qslots(S, c * N + no.L, 1));
+      uint32_t n = 0;
+#pragma unroll
+      for (int j = 0; j < F; ++j) {
+        if (active && (uint32_t)j + no.rc >= (uint32_t)F) {
+          uint4* dp = rp + 2 * n;
+          dp[0] = make_uint4(no.resA, RAFT_MSG_APPEND_RESPONSE | no.sid(j) << 3 | 1u << 7, no.T, 0);
+          dp[1] = make_uint4(0, 0, 0, 0);
+          ++n;
+        }
+      }
+    }
+#ifdef RS_WAVELOG
+    wl_lend = wall_clock64();                   // the image and the rings written
+    // some cluster of the wave had a round in progress at the launch's start or at its end
+    wl_cut = __builtin_amdgcn_ballot_w64(active && (lmid || no.qin || no.rc)) ? 1u : 0u;
+#endif
+  }
 
   // The steady certificate (device.hpp): a cluster the last steady launch left at its fixed point
   // with leader L needs only the first two lines. The rest is loaded when some cluster of the wave
@@ -484,6 +678,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   bool cert = false, full = false;
   if (!line0_wave) {
     load_line(1, true);
+#pragma unroll
+    for (int i = 32; i < NW4 * 4; ++i) w[i] = 0;
 #pragma unroll
     for (int i = 8; i < (NW4 < 16 ? NW4 : 16); ++i) {
       const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
@@ -520,7 +716,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   // (whatever else writes a ring clears the certificate), and so are its leader's commit (0) and
   // the rest of its state. It leaves every cluster with a strong certificate: the next launch
   // takes the line-0 path above. Any other wave takes the general path below.
-  bool lean = strong;
+  FixedPoint<N> fx;                           // (set below, by the waves that use it)
+  bool lean = false;
   if (!line0_wave) {
     lean = vouched && cfg_ok;
     lmid = 0;
@@ -588,7 +785,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
     for (int j = 0; j < F; ++j) lean = lean && fx.fdl[j] >= nxt;
   }
-  const bool lean_wave = !__builtin_amdgcn_ballot_w64(active && !lean);     // uniform
+  const bool lean_wave = !line0_wave && !__builtin_amdgcn_ballot_w64(active && !lean);   // uniform
   bool wb = false;
   if (lean_wave) {
 #ifdef RS_WAVELOG
@@ -641,31 +838,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       auto chunk = [&](int i) {
         return make_uint4(val(4 * i), val(4 * i + 1), val(4 * i + 2), val(4 * i + 3));
       };
-      // A line-0 wave has no old line 1 to compare with: line 0 goes through the image, and the
-      // chunks past it (the head and tail arrivals of messages in flight) change only for a
-      // cluster with a round in progress at the launch's start or its end -- stored below.
 #pragma unroll
       for (int i = (int)HOT_CW / 4; i < CH_END; ++i) {
-        if (i < 8 || !line0_wave) {                          // wave-uniform
-          const int q = 4 * i;
-          const uint4 x = chunk(i);
-          *lds_at<uint4>(img, img_off(lane, i)) = x;
-          dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3])
-                << (i / 8);
-        }
+        const int q = 4 * i;
+        const uint4 x = chunk(i);
+        *lds_at<uint4>(img, img_off(lane, i)) = x;
+        dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3])
+              << (i / 8);
       }
-      if (!line0_wave) {
-        // the strong certificate and the leader's term (device.hpp), one chunk
-        const uint32_t cn = CERT_STRONG | L;
-        *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) =
-            make_uint4(w[CL_CERT - 3], w[CL_CERT - 2], fx.Lterm, cn);
-        static_assert(CL_CTERM == CL_CERT - 1 && CL_CERT % 4 == 3, "one chunk");
-        dl |= (uint32_t)(cn != w[CL_CERT] || fx.Lterm != w[CL_CTERM]);
-      } else if (CH_END > 8 && (lmid || fx.qmask || fx.rmask)) {   // rare
-        uint4* const bp = reinterpret_cast<uint4*>(S.hot + (size_t)c * HB);
-#pragma unroll
-        for (int i = 8; i < CH_END; ++i) bp[i] = chunk(i);
-      }
+      // the strong certificate and the leader's term (device.hpp), one chunk
+      const uint32_t cn = CERT_STRONG | L;
+      *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) =
+          make_uint4(w[CL_CERT - 3], w[CL_CERT - 2], fx.Lterm, cn);
+      static_assert(CL_CTERM == CL_CERT - 1 && CL_CERT % 4 == 3, "one chunk");
+      dl |= (uint32_t)(cn != w[CL_CERT] || fx.Lterm != w[CL_CTERM]);
     }
     // messages in flight at the launch's end back to the rings, heads at slot 0 (rare)
     if (__builtin_amdgcn_ballot_w64(active && (fx.qmask || fx.rmask))) {   // wave-uniform
@@ -693,7 +879,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #ifdef RS_WAVELOG
     wl_lend = wall_clock64();                   // the image and the rings written
 #endif
-  } else {
+  } else if (!line0_wave) {
 #ifdef RS_WAVELOG
     wl_loop = wall_clock64();
 #endif
@@ -1635,7 +1821,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       rec[3] = make_uint4(wl_ph[0], wl_ph[1], wl_ph[2], wl_ph[3]);
       rec[4] = make_uint4(wl_ph[4], 0, 0, 0);
       rec[5] = make_uint4((uint32_t)(wl_x1 - wl_start), (uint32_t)(wl_x2 - wl_start),
-                          (uint32_t)(wl_x3 - wl_start), 0);
+                          (uint32_t)(wl_x3 - wl_start), wl_cut);
     }
   }
 #endif

@@ -41,6 +41,20 @@ if (a[:, 20] | a[:, 21] | a[:, 22]).any():   # fixed-point path stamps (round-5 
     print("  ..fp decided     us:", q((x2 - x1) / 100.0))
     print("  ..fp rounds done us:", q((x3 - x2) / 100.0))
     print("  ..general loop   us:", q((a[:, 9] - x3) / 100.0))
+    # the line-0 body flags a wave with some cluster in a round at the launch's start or its end
+    # (rec[5]'s last word): wave life and the five phases for the waves without and with one
+    cutw = a[:, 23] != 0
+    for nm, m in (("no cluster in a cut round", ~cutw), ("some cluster in a cut round", cutw)):
+        if not m.any():
+            print(f"  waves with {nm}: none")
+            continue
+        print(f"  waves with {nm}: {int(m.sum())}")
+        print("    life             us:", q((en - st)[m]))
+        print("    line 0 loaded    us:", q(a[m, 8] / 100.0))
+        print("    ..extracted      us:", q((x1 - a[:, 8])[m] / 100.0))
+        print("    ..rounds done    us:", q((x3 - x2)[m] / 100.0))
+        print("    ..image, rings   us:", q((a[:, 9] - x3)[m] / 100.0))
+        print("    ..lines stored   us:", q((end - start - a[:, 9])[m] / 100.0))
 print("lanes on    p0/10/50/90/99/100:", q(a[:, 7]))
 print("events/lane min p0/10/50/90/99/100:", q(a[:, 10]))
 print("events/lane max p0/10/50/90/99/100:", q(a[:, 11]))
