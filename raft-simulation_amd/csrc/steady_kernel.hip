@@ -1634,7 +1634,21 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           if (!ok) break;
           if (!rmask) resA = INF;
         }
-        if (at_fixed_point() && Ldl > tl) {
+        // The round finished here need not be on the period-P schedule. Responses that waited
+        // behind the leader's other events (an election's vote responses, one per tick), or a
+        // deadline the host wrote, put its next heartbeat after th + P, while el_base >= P keeps a
+        // follower's timer (>= t_ae + el_base) no earlier than th + P + d: with el_base at or near
+        // P it fires before the next append-entries. The cluster continues from the fixed point
+        // only if every follower's deadline (its lower bound, where the draw is owed) holds until
+        // that append-entries arrives (a tie: the message wins, SIM_SPEC P1) or to the launch's
+        // end; otherwise it is run tick by tick.
+        bool quiet = at_fixed_point() && Ldl > tl;
+        {
+          const uint32_t nxt = (uint32_t)min((uint64_t)Ldl + d, (uint64_t)tend);   // the next AE (or the end)
+#pragma unroll
+          for (int j = 0; j < F; ++j) quiet = quiet && fdl[j] >= nxt;
+        }
+        if (quiet) {
           fixed_point_rounds(Ldl);
           tl = tend - 1;
         }
