@@ -34,15 +34,6 @@ namespace rs {
 
 constexpr int LANE_WG = 256;                 // four waves, 64 clusters each
 
-// v = vals[k] for a runtime k < N, as masks (a select chain over an array is turned back into an
-// indexed load from memory by the compiler; this keeps the array in registers)
-template <int N>
-__device__ __forceinline__ uint32_t pick(const uint32_t (&vals)[N], uint32_t k) {
-  uint32_t v = 0;
-#pragma unroll
-  for (int i = 0; i < N; ++i) v |= vals[i] & (0u - (uint32_t)(k == (uint32_t)i));
-  return v;
-}
 // a ? x : y without a select the compiler could fold into an indexed load
 __device__ __forceinline__ uint32_t msel(bool a, uint32_t x, uint32_t y) {
   const uint32_t m = 0u - (uint32_t)a;
@@ -200,71 +191,75 @@ struct FixedPoint {
     }
     if (!rmask) resA = INF;
   }
-  // From the fixed point with the next heartbeat at th, every round to the launch's end: the rounds
-  // that end before it as trace hashes alone, then the one it cuts (heartbeat, append-entries and
-  // responses up to tend - 1; what is left stays queued as the general body leaves it). Every next
-  // event of the cluster is then at or after tend.
-  //
-  // The K whole rounds are one affine step of each hash (fixed_point_affine.hpp) when K is one of
-  // the two counts the wave's sets hold, as it is for every cluster on the schedule; when some lane
-  // here has another K (set_tick moved the clock, an election ended mid-launch, ...) all of them
-  // take the loop over rounds instead.
-  __device__ __forceinline__ void rounds(uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
-                                         uint32_t el_base, const BandSets& bs) {
-    const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1;
-    const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
-    const uint32_t tk = th + K * P;
-    if (K) {
-      const uint32_t K1 = bs.k[0].K1;
-      const bool top = K == K1;
-      if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
-        const SetWords sw = bs.k[top];                            // the lane's own set (K rounds)
-        const fpa::Half cl = sw.lead(), cf = sw.fol();
-        Ltr = fpa::apply_leader<F>(cl, Ltr, th, Lterm, L);
-        const uint64_t add = fpa::follower_addend<F>(cf, th, Lterm, L);
+  // what rounds() and run_launch() (below) ask of a lane state
+  __device__ __forceinline__ uint32_t term() const { return Lterm; }
+  __device__ __forceinline__ uint32_t sid(int j) const { return fk(j) + 1; }   // slot j's id
+  __device__ __forceinline__ void followers(uint64_t a, uint64_t add) {
 #pragma unroll
-        for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * cf.a + add;
-      } else {
-        // The trace hash is polynomial (device.hpp): a round's F + 1 leader events take the
-        // leader's hash h to h * M2^(F+1) + a, with a the Horner sum of the events' terms, and a
-        // round P ticks later adds P * M * (1 + M2 + ... + M2^F) to a; a follower's one event per
-        // round takes h to h * M2 + c, and c grows by P * M. One multiply-add per hash per round.
-        uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, Lterm, 0);
+    for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * a + add;
+  }
+  __device__ __forceinline__ void rearmed(uint32_t v) {   // by an append-entries; the draw owed
 #pragma unroll
-        for (int j = 0; j < F; ++j)
-          a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, fk(j) + 1, Lterm,
-                                        RAFT_LEADER, Lterm, 0);
-        const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
-        const uint64_t df = (uint64_t)P * TRACE_M;
-        uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, Lid, Lterm, RAFT_FOLLWER, Lterm, 0);
-        for (uint32_t r = 0; r < K; ++r) {
-          Ltr = Ltr * trace_pow<F + 1>() + a;
-          a += da;
+    for (int j = 0; j < F; ++j) fdl[j] = v;
+    fpend = (1u << F) - 1;
+  }
+  __device__ __forceinline__ void heartbeat(uint32_t ta) {   // its append-entries, arriving at ta
 #pragma unroll
-          for (int j = 0; j < F; ++j) ftr[j] = ftr[j] * TRACE_M2 + cf;
-          cf += df;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < F; ++j) fdl[j] = tk - P + d + el_base;   // + the owed draw
-      fpend = (1u << F) - 1;
-      Ldl = tk;                                   // = the last response + hb
-      nhb += K;
-      nae += F * K;
-      nar += F * K;
+    for (int j = 0; j < F; ++j) {
+      qA[j] = ta; qT[j] = Lterm; qa[j] = Lcommit; qb[j] = 0;
     }
-    if (tk < tend) {                              // the round the launch's end cuts
-      Ltr = trace_event(Ltr, tk, 7, 0, 0, RAFT_LEADER, Lterm, 0);
-      ++nhb;
-      Ldl = tk + hb;
+    qmask = (1u << F) - 1;
+  }
+  __device__ __forceinline__ bool queued() const { return rmask != 0; }   // responses still queued
+
+  // Write-back. Node k is the leader (k == L) or follower slot k - 1 (k > L) / k (k < L): x of that
+  // slot, both candidates at static indices.
+  __device__ __forceinline__ int slot(int k) const {
+    return (uint32_t)k > L ? (k > 0 ? k - 1 : 0) : (k < F ? k : F - 1);
+  }
+  __device__ __forceinline__ uint32_t at_node(const uint32_t (&x)[F], int k) const {
+    return msel((uint32_t)k > L, x[k > 0 ? k - 1 : 0], x[k < F ? k : F - 1]);
+  }
+  // node k's words of fields DEADLINE .. RES_TAIL into v[field][k]
+  template <int NV>
+  __device__ __forceinline__ void node_words(int k, uint32_t (&v)[NV][N]) const {
+    const bool isL = (uint32_t)k == L;
+    const int jl = k > 0 ? k - 1 : 0, jh = k < F ? k : F - 1;
+    const bool lo = (uint32_t)k > L;
+    const uint32_t fq = (qmask >> slot(k)) & 1, fqa = at_node(qA, k);
+    const uint64_t trf = (uint64_t)msel(lo, (uint32_t)(ftr[jl] >> 32), (uint32_t)(ftr[jh] >> 32)) << 32 |
+                         msel(lo, (uint32_t)ftr[jl], (uint32_t)ftr[jh]);
+    const uint64_t tr = isL ? Ltr : trf;
+    v[HF_DEADLINE][k] = isL ? Ldl : at_node(fdl, k);
+    v[HF_TRACE_LO][k] = (uint32_t)tr;
+    v[HF_TRACE_HI][k] = (uint32_t)(tr >> 32);
+    v[HF_QMETA][k] = isL ? pack_qmeta(0, 0, 0, __popc(rmask)) : pack_qmeta(0, fq, 0, 0);
+    v[HF_REQ_ARR][k] = isL ? INF : (fq ? fqa : INF);
+    v[HF_RES_ARR][k] = isL ? resA : INF;
+    v[HF_REQ_TAIL][k] = isL ? 0u : (fq ? fqa : 0u);
+    v[HF_RES_TAIL][k] = isL ? (rmask ? resA : 0u) : 0u;
+  }
+  // The messages in flight at the launch's end back to cluster c's rings, heads at slot 0 (rare).
+  // Every lane of the wave calls it; on: the lane's cluster is written back.
+  __device__ __forceinline__ void to_rings(const DevSim& S, uint32_t c, bool on) const {
+    if (!__builtin_amdgcn_ballot_w64(on && (qmask || rmask))) return;   // wave-uniform
 #pragma unroll
-      for (int j = 0; j < F; ++j) {
-        qA[j] = tk + d; qT[j] = Lterm; qa[j] = Lcommit; qb[j] = 0;
+    for (int j = 0; j < F; ++j) {
+      if (on && ((qmask >> j) & 1)) {
+        uint4* dp = reinterpret_cast<uint4*>(qslots(S, c * N + fk(j), 0));
+        dp[0] = make_uint4(qA[j], RAFT_MSG_APPEND_ENTRIES | Lid << 3, qT[j], qa[j]);
+        dp[1] = make_uint4(qb[j], 0, 0, 0);
       }
-      qmask = (1u << F) - 1;
-      if (tk + d < tend) {                        // the append-entries, then responses in time
-        append_entries(tk + d, d, el_base);
-        responses(tk, tend, d, hb);
+    }
+    uint4* rp = reinterpret_cast<uint4*>(qslots(S, c * N + L, 1));
+    uint32_t n = 0;
+#pragma unroll
+    for (int j = 0; j < F; ++j) {
+      if (on && ((rmask >> j) & 1)) {
+        uint4* dp = rp + 2 * n;
+        dp[0] = make_uint4(resA, RAFT_MSG_APPEND_RESPONSE | sid(j) << 3 | rH[j] << 7, rT[j], rA[j]);
+        dp[1] = make_uint4(rB[j], 0, 0, 0);
+        ++n;
       }
     }
   }
@@ -318,56 +313,128 @@ struct NodeOrder {
     }
     if (!rc) resA = INF;
   }
-  // FixedPoint::rounds on this state
-  __device__ __forceinline__ void rounds(uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
-                                         uint32_t el_base, const BandSets& bs) {
-    const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1;
-    const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
-    const uint32_t tk = th + K * P;
-    if (K) {
-      const uint32_t K1 = bs.k[0].K1;
-      const bool top = K == K1;
-      if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
-        const SetWords sw = bs.k[top];                            // the lane's own set (K rounds)
-        const fpa::Half cl = sw.lead(), cf = sw.fol();
-        Ltr = fpa::apply_leader<F>(cl, Ltr, th, T, L);
-        followers(cf.a, fpa::follower_addend<F>(cf, th, T, L));
-      } else {                                                    // round by round (FixedPoint)
-        uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, T, 0);
+  __device__ __forceinline__ uint32_t term() const { return T; }
+  __device__ __forceinline__ void rearmed(uint32_t v) { took = true; fdl = v; }
+  __device__ __forceinline__ void heartbeat(uint32_t ta) { qin = true; qA = ta; }
+  __device__ __forceinline__ bool queued() const { return rc != 0; }
+};
+
+// From the fixed point with the next heartbeat at th, every round to the launch's end: the rounds
+// that end before it as trace hashes alone, then the one it cuts (heartbeat, append-entries and
+// responses up to tend - 1; what is left stays queued as the general body leaves it). Every next
+// event of the cluster is then at or after tend. St: FixedPoint or NodeOrder.
+//
+// The K whole rounds are one affine step of each hash (fixed_point_affine.hpp) when K is one of
+// the two counts the wave's sets hold, as it is for every cluster on the schedule; when some lane
+// here has another K (set_tick moved the clock, an election ended mid-launch, ...) all of them
+// take the loop over rounds instead.
+template <typename St>
+__device__ __forceinline__ void rounds(St& s, uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
+                                       uint32_t el_base, const BandSets& bs) {
+  constexpr int F = St::F;
+  const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1, T = s.term();
+  const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
+  const uint32_t tk = th + K * P;
+  if (K) {
+    const uint32_t K1 = bs.k[0].K1;
+    const bool top = K == K1;
+    if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
+      const SetWords sw = bs.k[top];                            // the lane's own set (K rounds)
+      const fpa::Half cl = sw.lead(), cf = sw.fol();
+      s.Ltr = fpa::apply_leader<F>(cl, s.Ltr, th, T, s.L);
+      s.followers(cf.a, fpa::follower_addend<F>(cf, th, T, s.L));
+    } else {
+      // The trace hash is polynomial (device.hpp): a round's F + 1 leader events take the
+      // leader's hash h to h * M2^(F+1) + a, with a the Horner sum of the events' terms, and a
+      // round P ticks later adds P * M * (1 + M2 + ... + M2^F) to a; a follower's one event per
+      // round takes h to h * M2 + c, and c grows by P * M. One multiply-add per hash per round.
+      uint64_t a = trace_term(th, 7, 0, 0, RAFT_LEADER, T, 0);
 #pragma unroll
-        for (int j = 0; j < F; ++j)
-          a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, sid(j), T,
-                                        RAFT_LEADER, T, 0);
-        const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
-        const uint64_t df = (uint64_t)P * TRACE_M;
-        uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, L + 1, T, RAFT_FOLLWER, T, 0);
-        for (uint32_t r = 0; r < K; ++r) {
-          Ltr = Ltr * trace_pow<F + 1>() + a;
-          a += da;
-          followers(TRACE_M2, cf);
-          cf += df;
-        }
+      for (int j = 0; j < F; ++j)
+        a = a * TRACE_M2 + trace_term(th + 2 * d + j, RAFT_MSG_APPEND_RESPONSE, s.sid(j), T,
+                                      RAFT_LEADER, T, 0);
+      const uint64_t da = (uint64_t)P * (TRACE_M * trace_geo<F + 1>());
+      const uint64_t df = (uint64_t)P * TRACE_M;
+      uint64_t cf = trace_term(th + d, RAFT_MSG_APPEND_ENTRIES, s.L + 1, T, RAFT_FOLLWER, T, 0);
+      for (uint32_t r = 0; r < K; ++r) {
+        s.Ltr = s.Ltr * trace_pow<F + 1>() + a;
+        a += da;
+        s.followers(TRACE_M2, cf);
+        cf += df;
       }
-      took = true;
-      fdl = tk - P + d + el_base;                 // + the owed draw
-      Ldl = tk;                                   // = the last response + hb
-      nhb += K;
-      nae += F * K;
-      nar += F * K;
     }
-    if (tk < tend) {                              // the round the launch's end cuts
-      Ltr = trace_event(Ltr, tk, 7, 0, 0, RAFT_LEADER, T, 0);
-      ++nhb;
-      Ldl = tk + hb;
-      qin = true;
-      qA = tk + d;
-      if (tk + d < tend) {                        // the append-entries, then responses in time
-        append_entries(tk + d, d, el_base);
-        responses(tk, tend, d, hb);
-      }
+    s.rearmed(tk - P + d + el_base);              // by the last whole round's append-entries
+    s.Ldl = tk;                                   // = the last response + hb
+    s.nhb += K;
+    s.nae += F * K;
+    s.nar += F * K;
+  }
+  if (tk < tend) {                                // the round the launch's end cuts
+    s.Ltr = trace_event(s.Ltr, tk, 7, 0, 0, RAFT_LEADER, T, 0);
+    ++s.nhb;
+    s.Ldl = tk + hb;
+    s.heartbeat(tk + d);
+    if (tk + d < tend) {                          // the append-entries, then responses in time
+      s.append_entries(tk + d, d, el_base);
+      s.responses(tk, tend, d, hb);
     }
   }
+}
+
+// A launch from t0 for a cluster on the fixed point's schedule: the round in progress at t0 (mid:
+// 0 none, 1 its append-entries in flight, 2 its responses as the last launch's end cut them; its
+// heartbeat was at th0) to its end or the launch's, then the rounds from the next heartbeat.
+template <typename St>
+__device__ __forceinline__ void run_launch(St& s, uint32_t mid, uint32_t th0, uint32_t tend,
+                                           uint32_t d, uint32_t hb, uint32_t el_base, uint32_t P,
+                                           const BandSets& bs) {
+  bool whole = true;                              // the round in progress finished in this launch
+  if (mid == 1) {
+    if (th0 + d < tend) s.append_entries(th0 + d, d, el_base);
+    else whole = false;
+  }
+  if (mid && whole) {
+    s.responses(th0, tend, d, hb);
+    whole = !s.queued();
+  }
+  if (whole) rounds(s, mid ? th0 + P : th0, tend, d, hb, el_base, bs);
+}
+
+// Which round of the period-P schedule is in progress at t0, from the leader's deadline Ldl and
+// the messages in flight: the followers' request (req: present, arriving at reqA) or the nres
+// responses queued at the leader (arriving at resA). on: the cluster is on the schedule -- no
+// round (the next heartbeat at Ldl >= t0), append-entries not yet due, or responses exactly as the
+// last launch's end cut them; th0 is the round's heartbeat (mid = 0: the next one), nxt the
+// followers' next append-entries (or the launch's end): no follower's timer may fire before it.
+struct Schedule {
+  uint32_t mid, th0, nxt;
+  bool on;
 };
+template <int F>
+__device__ __forceinline__ Schedule schedule(uint32_t t0, uint32_t tend, uint32_t d, uint32_t hb,
+                                             uint32_t P, uint32_t Ldl, bool req, uint32_t reqA,
+                                             uint32_t nres, uint32_t resA) {
+  Schedule s{0, Ldl, 0, true};
+  if (req) {                                      // the append-entries in flight
+    s.mid = 1;
+    s.th0 = reqA - d;
+    s.on = reqA >= t0 && reqA >= d && Ldl == s.th0 + hb;
+  } else if (nres) {                              // the responses the last launch's end cut
+    s.mid = 2;
+    s.th0 = resA - 2 * d;
+    // the leader's deadline is the round's heartbeat + hb until it takes a response, then that
+    // response's tick (th + 2d + j0 - 1 for the j0-th) + hb
+    const uint32_t j0 = (uint32_t)F - nres;       // responses already taken
+    const int64_t cut = (int64_t)t0 - ((int64_t)s.th0 + 2 * d);   // what the last launch's end cut
+    s.on = resA >= 2 * d && (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut) &&
+           Ldl == (j0 ? s.th0 + 2 * d + j0 - 1 : s.th0) + hb;
+  } else {
+    s.on = Ldl >= t0;
+  }
+  s.nxt = min((s.mid == 2 ? s.th0 + P : s.th0) + d, tend);
+  return s;
+}
+
 
 template <int N>
 __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t t0, uint32_t nt) {
@@ -454,6 +521,28 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   };
   static_assert(IMGC >= 16, "lines 0 and 1 are whole in every block");
   uint32_t w[NW4 * 4];          // (the words past line 0 are set where a wave leaves the line-0 body)
+  auto read_chunks = [&](int lo, int hi) {              // chunks [lo, hi) of the image into w[]
+#pragma unroll
+    for (int i = lo; i < hi; ++i) {
+      const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
+      w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
+    }
+  };
+  // field f of node k; of the leader L; of follower slot j (node j below L, j + 1 from L on)
+  auto word = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
+  auto lword = [&](int f, uint32_t L) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) v |= word(f, k) & (0u - (uint32_t)(L == (uint32_t)k));
+    return v;
+  };
+  auto fword = [&](int f, int j, uint32_t L) {
+    return msel((uint32_t)j >= L, word(f, j + 1), word(f, j));
+  };
+  // the fields every path writes, DEADLINE .. RES_TAIL of every node, are whole chunks
+  static_assert(HF_RES_TAIL + 1 == HF_FLAGS && (HOT_CW + HF_FLAGS * N) % 4 == 0 && HOT_CW % 4 == 0,
+                "the fields written: DEADLINE .. RES_TAIL, whole chunks");
+  constexpr int CH_END = (int)(HOT_CW + HF_FLAGS * N) / 4;
   // The arguments the affine sets are built from, fetched with the ones the loads' addresses wait
   // for: one scalar round trip at the kernel's top, not a second one between the loads' issue and
   // the build (measured: DESIGN.md, "The line-0 body in node order").
@@ -480,11 +569,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     *S.nbail_zero = 0;
   }
   static_assert(NW4 >= 8, "line 0 is read whole");
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
-    w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
-  }
+  read_chunks(0, 8);
   const uint32_t tend = t0 + nt, d = S.dmin;
   const uint32_t P = 2 * d + F - 1 + S.hb, allF = (1u << F) - 1;
   uint32_t dl = 0, nhb = 0, nae = 0, nar = 0;  // lines of the block changed; events run
@@ -519,29 +604,22 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
                 (w[CL_CERT] & 0xFFFFu) < (uint32_t)N;
   {
     const uint32_t L = w[CL_CERT] & 0xFFFFu;
-    auto lw = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
-    auto lpick = [&](int f) {                       // field f of the leader
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < N; ++k) v |= lw(f, k) & (0u - (uint32_t)(L == (uint32_t)k));
-      return v;
-    };
     no.L = L; no.T = w[CL_CTERM];
-    no.Ldl = lpick(HF_DEADLINE);
-    no.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
+    no.Ldl = lword(HF_DEADLINE, L);
+    no.Ltr = (uint64_t)lword(HF_TRACE_HI, L) << 32 | lword(HF_TRACE_LO, L);
 #pragma unroll
-    for (int k = 0; k < N; ++k) no.tr[k] = (uint64_t)lw(HF_TRACE_HI, k) << 32 | lw(HF_TRACE_LO, k);
+    for (int k = 0; k < N; ++k) no.tr[k] = (uint64_t)word(HF_TRACE_HI, k) << 32 | word(HF_TRACE_LO, k);
     no.qin = no.took = false; no.qA = no.fdl = 0; no.rc = 0; no.resA = INF;
     no.nhb = no.nae = no.nar = 0;
-    const uint32_t Lqm = lpick(HF_QMETA), rsc = qm_res_cnt(Lqm);
+    const uint32_t Lqm = lword(HF_QMETA, L), rsc = qm_res_cnt(Lqm);
     // a certified block's rings have their heads at slot 0: the followers' QMETA words are all
     // "no message" or all "one request", the leader's is its response count
-    const uint32_t qm0 = L ? lw(HF_QMETA, 0) : lw(HF_QMETA, 1);   // the first follower's
+    const uint32_t qm0 = L ? word(HF_QMETA, 0) : word(HF_QMETA, 1);   // the first follower's
     const bool need = qm0 != 0;
     strong = strong && (qm0 & ~pack_qmeta(0, 1, 0, 0)) == 0 && Lqm == pack_qmeta(0, 0, 0, rsc) &&
              rsc <= (uint32_t)F && !(need && rsc);
 #pragma unroll
-    for (int k = 0; k < N; ++k) strong = strong && (L == (uint32_t)k || lw(HF_QMETA, k) == qm0);
+    for (int k = 0; k < N; ++k) strong = strong && (L == (uint32_t)k || word(HF_QMETA, k) == qm0);
     lth0 = no.Ldl;
     if (need) {                                     // the append-entries in flight
       lmid = 1;
@@ -571,7 +649,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     const uint32_t nxt = min((lmid == 2 ? lth0 + P : lth0) + d, tend);   // the next AE (or end)
 #pragma unroll
     for (int k = 0; k < N; ++k)
-      strong = strong && (L == (uint32_t)k || lw(HF_DEADLINE, k) >= nxt);
+      strong = strong && (L == (uint32_t)k || word(HF_DEADLINE, k) >= nxt);
   }
   const bool line0_wave = !__builtin_amdgcn_ballot_w64(active && !strong);   // uniform
   if (line0_wave) {
@@ -583,16 +661,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
 #endif
     if (active) {
-      bool whole = true;                      // the round in progress finished in this launch
-      if (lmid == 1) {
-        if (no.qA < tend) no.append_entries(no.qA, d, S.el_base);
-        else whole = false;
-      }
-      if (lmid && whole) {
-        no.responses(lth0, tend, d, S.hb);
-        whole = !no.rc;
-      }
-      if (whole) no.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base, bs);
+      run_launch(no, lmid, lth0, tend, d, S.hb, S.el_base, P, bs);
       nhb = no.nhb; nae = no.nae; nar = no.nar;
 #ifdef RS_WAVELOG
       asm volatile("" ::"v"(no.Ltr), "v"(no.tr[0]), "v"(no.Ldl));
@@ -618,9 +687,6 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           default: return isL ? Lrt : 0u;     // HF_RES_TAIL
         }
       };
-      static_assert(HF_RES_TAIL + 1 == HF_FLAGS, "the fields written: DEADLINE .. RES_TAIL");
-      static_assert((HOT_CW + HF_FLAGS * N) % 4 == 0 && HOT_CW % 4 == 0, "whole chunks");
-      constexpr int CH_END = (int)(HOT_CW + HF_FLAGS * N) / 4;
       auto chunk = [&](int i) {
         return make_uint4(val(4 * i), val(4 * i + 1), val(4 * i + 2), val(4 * i + 3));
       };
@@ -680,11 +746,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     load_line(1, true);
 #pragma unroll
     for (int i = 32; i < NW4 * 4; ++i) w[i] = 0;
-#pragma unroll
-    for (int i = 8; i < (NW4 < 16 ? NW4 : 16); ++i) {
-      const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
-      w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
-    }
+    read_chunks(8, NW4 < 16 ? NW4 : 16);
     uint32_t nlc = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -698,11 +760,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     full = IMGC > 16 && __builtin_amdgcn_ballot_w64(active && !cert) != 0;   // uniform
     if (full) {
       load_half1();
-#pragma unroll
-      for (int i = 16; i < NW4; ++i) {
-        const uint4 x = *lds_at<const uint4>(img, img_off(lane, i));
-        w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
-      }
+      read_chunks(16, NW4);
     }
   }
   const bool vouched = cert && !full;         // its lines past the second are the fixed point's
@@ -711,8 +769,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   // A wave whose every cluster is vouched for by a certificate (device.hpp), on the fixed
   // point's period-P schedule (its round in progress at t0: none, the append-entries in flight, or
   // the responses the last launch's end cut) and with its followers' draws owed (FL_DRAW) runs the
-  // whole launch from the first two lines of its blocks: the rest of that round, then
-  // FixedPoint::rounds. Queued messages are not read: a certified cluster's are the fixed point's
+  // whole launch from the first two lines of its blocks: the rest of that round, then the
+  // rounds (run_launch). Queued messages are not read: a certified cluster's are the fixed point's
   // (whatever else writes a ring clears the certificate), and so are its leader's commit (0) and
   // the rest of its state. It leaves every cluster with a strong certificate: the next launch
   // takes the line-0 path above. Any other wave takes the general path below.
@@ -720,70 +778,49 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   bool lean = false;
   if (!line0_wave) {
     lean = vouched && cfg_ok;
-    lmid = 0;
     const uint32_t L = Lc;
-    auto lw = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
-    auto lpick = [&](int f) {                       // field f of the leader
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < N; ++k) v |= lw(f, k) & (0u - (uint32_t)(L == (uint32_t)k));
-      return v;
-    };
-    auto lfol = [&](int f, int j) {                 // field f of follower slot j
-      const uint32_t m = 0u - (uint32_t)((uint32_t)j >= L);
-      return (lw(f, j + 1) & m) | (lw(f, j) & ~m);
-    };
-    fx.L = L; fx.Lid = L + 1; fx.Lterm = lpick(HF_TERM); fx.Lcommit = 0;
-    fx.Ldl = lpick(HF_DEADLINE);
-    fx.Ltr = (uint64_t)lpick(HF_TRACE_HI) << 32 | lpick(HF_TRACE_LO);
+    fx.L = L; fx.Lid = L + 1; fx.Lterm = lword(HF_TERM, L); fx.Lcommit = 0;
+    fx.Ldl = lword(HF_DEADLINE, L);
+    fx.Ltr = (uint64_t)lword(HF_TRACE_HI, L) << 32 | lword(HF_TRACE_LO, L);
     fx.qmask = fx.rmask = 0; fx.resA = INF; fx.fpend = allF; fx.nhb = fx.nae = fx.nar = 0;
-    const uint32_t Lqm = lpick(HF_QMETA);
+    const uint32_t Lqm = lword(HF_QMETA, L);
     const uint32_t rsc = qm_res_cnt(Lqm);
     uint32_t need = 0;
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-      fx.fdl[j] = lfol(HF_DEADLINE, j);
-      fx.ftr[j] = (uint64_t)lfol(HF_TRACE_HI, j) << 32 | lfol(HF_TRACE_LO, j);
-      const uint32_t qm = lfol(HF_QMETA, j);
+      fx.fdl[j] = fword(HF_DEADLINE, j, L);
+      fx.ftr[j] = (uint64_t)fword(HF_TRACE_HI, j, L) << 32 | fword(HF_TRACE_LO, j, L);
+      const uint32_t qm = fword(HF_QMETA, j, L);
       // (qm >> 4) & 31 is qm_req_cnt(qm), spelled out: through the reader the kernel's code changes
-      lean = lean && (lfol(HF_FLAGS, j) & FL_DRAW) && ((qm >> 4) & 31) <= 1 && !qm_res_cnt(qm);
+      lean = lean && (fword(HF_FLAGS, j, L) & FL_DRAW) && ((qm >> 4) & 31) <= 1 && !qm_res_cnt(qm);
       need |= (qm_req_cnt(qm) ? 1u : 0u) << j;
       fx.qA[j] = INF; fx.qT[j] = fx.qa[j] = fx.qb[j] = 0;
       fx.rT[j] = fx.rA[j] = fx.rB[j] = fx.rH[j] = 0;
     }
     lean = lean && !qm_req_cnt(Lqm) && rsc <= (uint32_t)F && !(need && rsc) &&
            (need == 0 || need == allF);
-    lth0 = fx.Ldl;
-    if (need) {                                     // the append-entries in flight
-      lmid = 1;
-      const uint32_t ta = lfol(HF_REQ_ARR, 0);
-      lth0 = ta - d;
-      lean = lean && ta >= t0 && ta >= d && fx.Ldl == lth0 + S.hb;
+    const uint32_t ta = fword(HF_REQ_ARR, 0, L), ra = lword(HF_RES_ARR, L);
+    const Schedule sc = schedule<F>(t0, tend, d, S.hb, P, fx.Ldl, need != 0, ta, rsc, ra);
+    lean = lean && sc.on;
+    lmid = sc.mid;
+    lth0 = sc.th0;
+    if (lmid == 1) {                                // every follower holds the append-entries
 #pragma unroll
       for (int j = 0; j < F; ++j) {
-        lean = lean && lfol(HF_REQ_ARR, j) == ta;
+        lean = lean && fword(HF_REQ_ARR, j, L) == ta;
         fx.qA[j] = ta; fx.qT[j] = fx.Lterm;
       }
       fx.qmask = allF;
-    } else if (rsc) {                               // the responses the last launch's end cut
-      lmid = 2;
-      const uint32_t ra = lpick(HF_RES_ARR), j0 = (uint32_t)F - rsc;
-      lth0 = ra - 2 * d;
-      const int64_t cut = (int64_t)t0 - ((int64_t)lth0 + 2 * d);
-      lean = lean && ra >= 2 * d && (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut) &&
-             fx.Ldl == (j0 ? lth0 + 2 * d + j0 - 1 : lth0) + S.hb;
-      fx.rmask = allF & ~((1u << j0) - 1);
+    } else if (lmid == 2) {                         // the last rsc slots' responses, successful
+      fx.rmask = allF & ~((1u << ((uint32_t)F - rsc)) - 1);
       fx.resA = ra;
 #pragma unroll
       for (int j = 0; j < F; ++j) {
         fx.rT[j] = fx.Lterm; fx.rH[j] = 1;
       }
-    } else {
-      lean = lean && fx.Ldl >= t0;
     }
-    const uint32_t nxt = min((lmid == 2 ? lth0 + P : lth0) + d, tend);   // the next AE (or end)
 #pragma unroll
-    for (int j = 0; j < F; ++j) lean = lean && fx.fdl[j] >= nxt;
+    for (int j = 0; j < F; ++j) lean = lean && fx.fdl[j] >= sc.nxt;
   }
   const bool lean_wave = !line0_wave && !__builtin_amdgcn_ballot_w64(active && !lean);   // uniform
   bool wb = false;
@@ -793,47 +830,16 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
 #endif
     if (active) {
-      bool whole = true;                      // the round in progress finished in this launch
-      if (lmid == 1) {
-        if (fx.qA[0] < tend) fx.append_entries(fx.qA[0], d, S.el_base);
-        else whole = false;
-      }
-      if (lmid && whole) {
-        fx.responses(lth0, tend, d, S.hb);
-        whole = !fx.rmask;
-      }
-      if (whole) fx.rounds(lmid ? lth0 + P : lth0, tend, d, S.hb, S.el_base, bs);
+      run_launch(fx, lmid, lth0, tend, d, S.hb, S.el_base, P, bs);
       nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
 #ifdef RS_WAVELOG
       asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
       wl_x3 = wall_clock64();                 // the rounds done
 #endif
       // fields DEADLINE .. RES_TAIL of every node back into the image (the rest is unchanged)
-      const uint32_t L = fx.L;
       uint32_t v[HF_FLAGS][N];
 #pragma unroll
-      for (int k = 0; k < N; ++k) {
-        const bool isL = (uint32_t)k == L;
-        const int jl = k > 0 ? k - 1 : 0, jh = k < F ? k : F - 1;
-        const bool lo = (uint32_t)k > L;
-        auto fv = [&](const uint32_t* x) { return msel(lo, x[jl], x[jh]); };
-        const uint32_t fq = (fx.qmask >> (lo ? jl : jh)) & 1, fqa = fv(fx.qA);
-        const uint64_t trf = (uint64_t)msel(lo, (uint32_t)(fx.ftr[jl] >> 32),
-                                            (uint32_t)(fx.ftr[jh] >> 32)) << 32 |
-                             msel(lo, (uint32_t)fx.ftr[jl], (uint32_t)fx.ftr[jh]);
-        const uint64_t tr = isL ? fx.Ltr : trf;
-        v[HF_DEADLINE][k] = isL ? fx.Ldl : fv(fx.fdl);
-        v[HF_TRACE_LO][k] = (uint32_t)tr;
-        v[HF_TRACE_HI][k] = (uint32_t)(tr >> 32);
-        v[HF_QMETA][k] = isL ? pack_qmeta(0, 0, 0, __popc(fx.rmask)) : pack_qmeta(0, fq, 0, 0);
-        v[HF_REQ_ARR][k] = isL ? INF : (fq ? fqa : INF);
-        v[HF_RES_ARR][k] = isL ? fx.resA : INF;
-        v[HF_REQ_TAIL][k] = isL ? 0u : (fq ? fqa : 0u);
-        v[HF_RES_TAIL][k] = isL ? (fx.rmask ? fx.resA : 0u) : 0u;
-      }
-      // (HOT_CW + HF_FLAGS * N is a multiple of 4 for every N: these chunks hold no other word)
-      static_assert((HOT_CW + HF_FLAGS * N) % 4 == 0 && HOT_CW % 4 == 0, "whole chunks");
-      constexpr int CH_END = (int)(HOT_CW + HF_FLAGS * N) / 4;
+      for (int k = 0; k < N; ++k) fx.node_words(k, v);
       auto val = [&](int q) { return v[(q - HOT_CW) / N][(q - HOT_CW) % N]; };
       auto chunk = [&](int i) {
         return make_uint4(val(4 * i), val(4 * i + 1), val(4 * i + 2), val(4 * i + 3));
@@ -847,35 +853,13 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
               << (i / 8);
       }
       // the strong certificate and the leader's term (device.hpp), one chunk
-      const uint32_t cn = CERT_STRONG | L;
+      const uint32_t cn = CERT_STRONG | fx.L;
       *lds_at<uint4>(img, img_off(lane, CL_CERT / 4)) =
           make_uint4(w[CL_CERT - 3], w[CL_CERT - 2], fx.Lterm, cn);
       static_assert(CL_CTERM == CL_CERT - 1 && CL_CERT % 4 == 3, "one chunk");
       dl |= (uint32_t)(cn != w[CL_CERT] || fx.Lterm != w[CL_CTERM]);
     }
-    // messages in flight at the launch's end back to the rings, heads at slot 0 (rare)
-    if (__builtin_amdgcn_ballot_w64(active && (fx.qmask || fx.rmask))) {   // wave-uniform
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        if (active && ((fx.qmask >> j) & 1)) {
-          uint4* dp = reinterpret_cast<uint4*>(qslots(S, c * N + fx.fk(j), 0));
-          dp[0] = make_uint4(fx.qA[j], RAFT_MSG_APPEND_ENTRIES | fx.Lid << 3, fx.qT[j], fx.qa[j]);
-          dp[1] = make_uint4(fx.qb[j], 0, 0, 0);
-        }
-      }
-      uint4* rp = reinterpret_cast<uint4*>(qslots(S, c * N + fx.L, 1));
-      uint32_t n = 0;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        if (active && ((fx.rmask >> j) & 1)) {
-          uint4* dp = rp + 2 * n;
-          dp[0] = make_uint4(fx.resA, RAFT_MSG_APPEND_RESPONSE | (fx.fk(j) + 1) << 3 | fx.rH[j] << 7,
-                             fx.rT[j], fx.rA[j]);
-          dp[1] = make_uint4(fx.rB[j], 0, 0, 0);
-          ++n;
-        }
-      }
-    }
+    fx.to_rings(S, c, active);
 #ifdef RS_WAVELOG
     wl_lend = wall_clock64();                   // the image and the rings written
 #endif
@@ -883,10 +867,6 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #ifdef RS_WAVELOG
     wl_loop = wall_clock64();
 #endif
-    auto field = [&](int f, uint32_t (&out)[N]) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) out[k] = w[HOT_CW + f * N + k];
-    };
     // ------------------------------------------- the election from init-node, in closed form
     // A cluster still in init-node's state (core.clj:31-38: every node a follower of the same term
     // with no vote, leader, log, leader-state or message; no checker mark) elects the node whose
@@ -1118,14 +1098,11 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         }
       }
     }
-    uint32_t nfl[N], nqm[N];
-    field(HF_FLAGS, nfl);
-    field(HF_QMETA, nqm);
     // exactly one leader; every node running; only the leader has leader-state
     uint32_t L = 0, nlead = 0, badn = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      const uint32_t f = nfl[k];
+      const uint32_t f = word(HF_FLAGS, k);
       const bool lead = fl_role(f) == RAFT_LEADER;
       L = lead ? (uint32_t)k : L;
       nlead += lead;
@@ -1133,66 +1110,32 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     }
     bool bad = !active || nlead != 1 || badn != 0 || S.Q < (uint32_t)F;
     const uint32_t Lid = L + 1;
-    // follower slot j is node j (j < L) or j + 1 (j >= L)
-    auto fsel = [&](const uint32_t (&v)[N], int j) { return msel((uint32_t)j >= L, v[j + 1], v[j]); };
-    auto fk = [&](int j) { return (uint32_t)j + ((uint32_t)j >= L ? 1u : 0u); };
-
-    uint32_t tmp[N];
-    // leader registers
-    const uint32_t Lfl = pick<N>(nfl, L);
-    field(HF_MASKS, tmp); uint32_t Lmk = pick<N>(tmp, L);
-    uint32_t fmk[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) fmk[j] = fsel(tmp, j);
-    field(HF_TERM, tmp); const uint32_t Lterm = pick<N>(tmp, L);
-    uint32_t fterm[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) fterm[j] = fsel(tmp, j);
-    field(HF_COMMIT, tmp); const uint32_t Lcommit = pick<N>(tmp, L);
-    uint32_t fcommit[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) fcommit[j] = fsel(tmp, j);
-    field(HF_LEN, tmp); const uint32_t Llen = pick<N>(tmp, L);
-    uint32_t flen[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) flen[j] = fsel(tmp, j);
-    field(HF_DEADLINE, tmp); uint32_t Ldl = pick<N>(tmp, L);
-    uint32_t fdl[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) fdl[j] = fsel(tmp, j);
-    uint32_t tlo[N], thi[N];
-    field(HF_TRACE_LO, tlo);
-    field(HF_TRACE_HI, thi);
-    uint64_t Ltr = (uint64_t)pick<N>(thi, L) << 32 | pick<N>(tlo, L);
-    uint64_t ftr[F];
-    uint32_t ffl[F];
+    // The leader's registers and, per follower slot, the followers'. What the fixed point's events
+    // change -- deadlines, trace hashes, the messages in flight, the counters -- is fx's, so those
+    // events (run_launch, rounds) run on this path's state as it stands.
+    const uint32_t Lfl = lword(HF_FLAGS, L), Lterm = lword(HF_TERM, L);
+    const uint32_t Lcommit = lword(HF_COMMIT, L), Llen = lword(HF_LEN, L);
+    uint32_t Lmk = lword(HF_MASKS, L);
+    fx.L = L; fx.Lid = Lid; fx.Lterm = Lterm; fx.Lcommit = Lcommit;
+    fx.Ldl = lword(HF_DEADLINE, L);
+    fx.Ltr = (uint64_t)lword(HF_TRACE_HI, L) << 32 | lword(HF_TRACE_LO, L);
+    fx.nhb = nhb; fx.nae = nae; fx.nar = nar;        // (an election's, above)
+    uint32_t ffl[F], fmk[F], fterm[F], fcommit[F], flen[F];
+    // the leader's rows for its followers: next_index / match_index of peer id fk(j) + 1; and as
+    // loaded: unchanged words are not stored back
+    int32_t nx[F], mt[F], nx0[F], mt0[F];
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-      ftr[j] = (uint64_t)fsel(thi, j) << 32 | fsel(tlo, j);
-      ffl[j] = fsel(nfl, j);
-    }
-    // the leader's rows for its followers: next_index / match_index of peer id fk(j) + 1
-    int32_t nx[F], mt[F];
-    {
-      uint32_t rn[N], rm[N];                    // the leader's next / match of each peer id p + 1
-#pragma unroll
-      for (int p = 0; p < N; ++p) {
-        field(HF_NEXT + p, tmp);
-        rn[p] = pick<N>(tmp, L);
-        field(HF_NEXT + N + p, tmp);
-        rm[p] = pick<N>(tmp, L);
-      }
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        nx[j] = (int32_t)fsel(rn, j);
-        mt[j] = (int32_t)fsel(rm, j);
-      }
-    }
-    int32_t nx0[F], mt0[F];                     // as loaded: unchanged words are not stored back
-#pragma unroll
-    for (int j = 0; j < F; ++j) {
-      nx0[j] = nx[j];
-      mt0[j] = mt[j];
+      ffl[j] = fword(HF_FLAGS, j, L);
+      fmk[j] = fword(HF_MASKS, j, L);
+      fterm[j] = fword(HF_TERM, j, L);
+      fcommit[j] = fword(HF_COMMIT, j, L);
+      flen[j] = fword(HF_LEN, j, L);
+      fx.fdl[j] = fword(HF_DEADLINE, j, L);
+      fx.ftr[j] = (uint64_t)fword(HF_TRACE_HI, j, L) << 32 | fword(HF_TRACE_LO, j, L);
+      const bool up = (uint32_t)j >= L;
+      nx[j] = nx0[j] = (int32_t)msel(up, lword(HF_NEXT + j + 1, L), lword(HF_NEXT + j, L));
+      mt[j] = mt0[j] = (int32_t)msel(up, lword(HF_NEXT + N + j + 1, L), lword(HF_NEXT + N + j, L));
     }
     const bool ackbad = Llen > w[CL_HWM_IDX];          // a success response would be checker work (P4)
     const uint32_t Lkeys = Lmk >> 16;
@@ -1203,25 +1146,24 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           (Lfl & FL_SEQ) || Lcommit > Llen;
 
 #ifdef RS_WAVELOG
-    asm volatile("" ::"v"(Ltr), "v"(fdl[0]), "v"(nx[0]));
+    asm volatile("" ::"v"(fx.Ltr), "v"(fx.fdl[0]), "v"(nx[0]));
     wl_x1 = wall_clock64();                     // fields extracted
 #endif
     // ---------------------------------------------------------------- queued messages
-    uint32_t qmask = 0, rmask = 0, resA = INF;
-    uint32_t qA[F], qT[F], qa[F], qb[F], rT[F], rA[F], rB[F], rH[F];
+    fx.qmask = 0; fx.rmask = 0; fx.resA = INF;
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-      qA[j] = INF; qT[j] = qa[j] = qb[j] = 0;
-      rT[j] = rA[j] = rB[j] = rH[j] = 0;
+      fx.qA[j] = INF; fx.qT[j] = fx.qa[j] = fx.qb[j] = 0;
+      fx.rT[j] = fx.rA[j] = fx.rB[j] = fx.rH[j] = 0;
     }
     if (!bad) {
-      const uint32_t Lqm = pick<N>(nqm, L);
+      const uint32_t Lqm = lword(HF_QMETA, L);
       bad = qm_req_cnt(Lqm);                                   // the leader's REQ queue is empty
       const uint32_t rsh = qm_res_head(Lqm), rsc = qm_res_cnt(Lqm);
       uint32_t need = 0, rqh[F];
 #pragma unroll
       for (int j = 0; j < F; ++j) {
-        const uint32_t qm = fsel(nqm, j);
+        const uint32_t qm = fword(HF_QMETA, j, L);
         const uint32_t rqc = qm_req_cnt(qm);
         rqh[j] = qm_req_head(qm);
         bad = bad || rqc > 1 || qm_res_cnt(qm) != 0;       // <= 1 request, no responses
@@ -1237,7 +1179,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
         for (int j = 0; j < F; ++j) {                          // the leader's append-entries
           const uint4* mp = reinterpret_cast<const uint4*>(
-              qslots(S, c * N + fk(j), 0) + min(rqh[j], S.Q - 1) * qstride(S, 0));
+              qslots(S, c * N + fx.fk(j), 0) + min(rqh[j], S.Q - 1) * qstride(S, 0));
           qm0[j] = mp[0];
           qm1[j] = mp[1];
         }
@@ -1255,8 +1197,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           if ((need >> j) & 1) {
             const uint4 m0 = qm0[j], m1 = qm1[j];
             bad = bad || m0.y != (RAFT_MSG_APPEND_ENTRIES | Lid << 3) || m1.y || m1.z || m1.w;
-            qmask |= 1u << j;
-            qA[j] = m0.x; qT[j] = m0.z; qa[j] = m0.w; qb[j] = m1.x;
+            fx.qmask |= 1u << j;
+            fx.qA[j] = m0.x; fx.qT[j] = m0.z; fx.qa[j] = m0.w; fx.qb[j] = m1.x;
           }
         }
         uint32_t last = 0;
@@ -1266,23 +1208,23 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
             const uint4 m0 = rm0[i], m1 = rm1[i];
             const uint32_t hdr = m0.y, src = (hdr >> 3) & 15;
             bad = (hdr & 7) != RAFT_MSG_APPEND_RESPONSE || (hdr >> 8) || m1.y || m1.z || m1.w ||
-                  src <= last || src > (uint32_t)N || src == Lid || (i && m0.x != resA);
+                  src <= last || src > (uint32_t)N || src == Lid || (i && m0.x != fx.resA);
             last = src;
-            resA = m0.x;
+            fx.resA = m0.x;
             const uint32_t j = src - 1 - (src > Lid ? 1u : 0u);
             if (!bad) {
-              rmask |= 1u << j;
+              fx.rmask |= 1u << j;
 #pragma unroll
               for (int jj = 0; jj < F; ++jj) {
                 if ((uint32_t)jj == j) {
-                  rT[jj] = m0.z; rA[jj] = m0.w; rB[jj] = m1.x; rH[jj] = (hdr >> 7) & 1;
+                  fx.rT[jj] = m0.z; fx.rA[jj] = m0.w; fx.rB[jj] = m1.x; fx.rH[jj] = (hdr >> 7) & 1;
                 }
               }
             }
           }
         }
       }
-      if (!rmask) resA = INF;
+      if (!fx.rmask) fx.resA = INF;
     }
     record_bail(active && bad, t0);           // outside the model from the start: bail at t0
     wb = active && !bad;
@@ -1292,23 +1234,23 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     uint32_t tn = t0;
     // followers whose deadline holds its lower bound t_ae + el_base (the draw is deferred)
     // (a draw owed from an earlier launch: FL_DRAW in the follower's flags, device.hpp)
-    uint32_t fpend = 0;
+    fx.fpend = 0;
 #pragma unroll
-    for (int j = 0; j < F; ++j) fpend |= ((ffl[j] & FL_DRAW) ? 1u : 0u) << j;
+    for (int j = 0; j < F; ++j) fx.fpend |= ((ffl[j] & FL_DRAW) ? 1u : 0u) << j;
     auto draw_deadlines = [&](uint32_t due) {
 #pragma unroll
       for (int j = 0; j < F; ++j) {
         if ((due >> j) & 1) {
-          const uint4 wd = event_draw(g, fk(j) + 1, fdl[j] - S.el_base, S);   // D4, core.clj:174
-          fdl[j] += __umulhi(wd.y, S.el_span);
+          const uint4 wd = event_draw(g, fx.fk(j) + 1, fx.fdl[j] - S.el_base, S);   // D4, core.clj:174
+          fx.fdl[j] += __umulhi(wd.y, S.el_span);
         }
       }
-      fpend &= ~due;
+      fx.fpend &= ~due;
     };
     auto next_event = [&]() {
-      uint32_t m = min(Ldl, resA);
+      uint32_t m = min(fx.Ldl, fx.resA);
 #pragma unroll
-      for (int j = 0; j < F; ++j) m = min(m, min(fdl[j], qA[j]));
+      for (int j = 0; j < F; ++j) m = min(m, min(fx.fdl[j], fx.qA[j]));
       return m;
     };
     // The cluster at its fixed point: every follower took the leader's append-entries (flags,
@@ -1329,69 +1271,36 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       return ok;
     };
     auto at_fixed_point = [&]() {
-      return S.el_base >= P && S.hb >= 2 * d + F && !qmask && !rmask && at_fixed_point_state();
+      return S.el_base >= P && S.hb >= 2 * d + F && !fx.qmask && !fx.rmask && at_fixed_point_state();
     };
-    // From the fixed point with the next heartbeat at th, every round to the launch's end as trace
-    // hashes: the rounds that end before it, then the one it cuts (heartbeat, append-entries and
-    // responses up to tend - 1; what is left is queued as the general body leaves it): every next
-    // event of the cluster is then at or after tend.
-    auto fixed_point_rounds = [&](uint32_t th) {   // FixedPoint::rounds on this path's registers
-      FixedPoint<N> x;
-      x.L = L; x.Lid = Lid; x.Lterm = Lterm; x.Lcommit = Lcommit;
-      x.Ltr = Ltr; x.Ldl = Ldl; x.fpend = fpend; x.qmask = qmask; x.rmask = rmask; x.resA = resA;
-      x.nhb = nhb; x.nae = nae; x.nar = nar;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        x.ftr[j] = ftr[j]; x.fdl[j] = fdl[j];
-        x.qA[j] = qA[j]; x.qT[j] = qT[j]; x.qa[j] = qa[j]; x.qb[j] = qb[j];
-        x.rT[j] = rT[j]; x.rA[j] = rA[j]; x.rB[j] = rB[j]; x.rH[j] = rH[j];
-      }
-      x.rounds(th, tend, d, S.hb, S.el_base, bs);
-      Ltr = x.Ltr; Ldl = x.Ldl; fpend = x.fpend; qmask = x.qmask; rmask = x.rmask; resA = x.resA;
-      nhb = x.nhb; nae = x.nae; nar = x.nar;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        ftr[j] = x.ftr[j]; fdl[j] = x.fdl[j];
-        qA[j] = x.qA[j]; qT[j] = x.qT[j]; qa[j] = x.qa[j]; qb[j] = x.qb[j];
-        rT[j] = x.rT[j]; rA[j] = x.rA[j]; rB[j] = x.rB[j]; rH[j] = x.rH[j];
-      }
-    };
+    auto fixed_point_rounds = [&](uint32_t th) { rounds(fx, th, tend, d, S.hb, S.el_base, bs); };
 
     // ------------------------------------------- the fixed-point path (C2's steady state)
     // A cluster at its fixed point (above) whose round in progress at t0 is on the period-P
     // schedule -- none (the next heartbeat at Ldl >= t0), its append-entries in flight, or its
     // responses pending exactly as the last launch's end cut them -- and whose followers' timers
     // cannot fire before their next append-entries runs every event of the launch here: the rest
-    // of that round event by event, then fixed_point_rounds. Everything else is the general loop's.
+    // of that round, then the rounds (run_launch). Everything else is the general loop's.
     bool fp = wb && S.el_base >= P && S.hb >= 2 * d + F && (vouched || at_fixed_point_state());
-    uint32_t th0 = Ldl, mid = 0;               // the round's heartbeat; 1 AEs in flight, 2 responses
-    if (qmask) {
-      mid = 1;
-      th0 = qA[0] - d;
-      fp = fp && qmask == allF && !rmask && qA[0] >= t0 && qA[0] >= d && Ldl == th0 + S.hb;
+    // (the round's heartbeat th0; mid: 1 append-entries in flight, 2 responses)
+    const Schedule sc = schedule<F>(t0, tend, d, S.hb, P, fx.Ldl, fx.qmask != 0, fx.qA[0],
+                                    __popc(fx.rmask), fx.resA);
+    const uint32_t th0 = sc.th0, mid = sc.mid;
+    fp = fp && sc.on;
+    if (mid == 1) {                            // every follower holds the same empty append-entries
+      fp = fp && fx.qmask == allF && !fx.rmask;
 #pragma unroll
       for (int j = 0; j < F; ++j)
-        fp = fp && qA[j] == qA[0] && qT[j] == Lterm && qa[j] == Lcommit && qb[j] == 0;
-    } else if (rmask) {
-      mid = 2;
-      th0 = resA - 2 * d;
-      const uint32_t j0 = (uint32_t)F - __popc(rmask);          // responses already taken
-      const int64_t cut = (int64_t)t0 - ((int64_t)th0 + 2 * d);  // what the last launch's end cut
-      fp = fp && resA >= 2 * d && rmask == (allF & ~((1u << j0) - 1)) &&
-           (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut) &&
-           Ldl == (j0 ? th0 + 2 * d + j0 - 1 : th0) + S.hb;
+        fp = fp && fx.qA[j] == fx.qA[0] && fx.qT[j] == Lterm && fx.qa[j] == Lcommit && fx.qb[j] == 0;
+    } else if (mid == 2) {                     // the last slots' responses, successful
+      fp = fp && fx.rmask == (allF & ~((1u << ((uint32_t)F - __popc(fx.rmask))) - 1));
 #pragma unroll
       for (int j = 0; j < F; ++j)
-        fp = fp && (!((rmask >> j) & 1) ||
-                    (rT[j] == Lterm && rA[j] == Lcommit && rB[j] == 0 && rH[j] == 1));
-    } else {
-      fp = fp && Ldl >= t0;
+        fp = fp && (!((fx.rmask >> j) & 1) ||
+                    (fx.rT[j] == Lterm && fx.rA[j] == Lcommit && fx.rB[j] == 0 && fx.rH[j] == 1));
     }
-    {
-      const uint32_t nxt = min((mid == 2 ? th0 + P : th0) + d, tend);   // the next AE (or the end)
 #pragma unroll
-      for (int j = 0; j < F; ++j) fp = fp && fdl[j] >= nxt;
-    }
+    for (int j = 0; j < F; ++j) fp = fp && fx.fdl[j] >= sc.nxt;
     // A vouched cluster off the fixed-point path (set_tick moved the clock, ...) has no full state
     // here: the general body runs it from t0.
     const bool vbail = vouched && wb && !fp;
@@ -1403,46 +1312,10 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #endif
     if (fp) {
       run = false;
-      bool whole = true;                        // the round in progress finished in this launch
-      if (mid == 1) {
-        const uint32_t ta = qA[0];
-        if (ta < tend) {                        // the append-entries
-#pragma unroll
-          for (int j = 0; j < F; ++j) {
-            ftr[j] = trace_event(ftr[j], ta, RAFT_MSG_APPEND_ENTRIES, Lid, Lterm, RAFT_FOLLWER,
-                                 Lterm, 0);
-            fdl[j] = ta + S.el_base;
-            qA[j] = INF;
-            rT[j] = Lterm; rA[j] = Lcommit; rB[j] = 0; rH[j] = 1;
-          }
-          fpend = allF;
-          qmask = 0;
-          rmask = allF;
-          resA = ta + d;
-          nae += F;
-        } else {
-          whole = false;
-        }
-      }
-      if (mid && whole) {                       // the responses, one per tick in slot order
-#pragma unroll
-        for (int j = 0; j < F; ++j) {
-          const uint32_t tau = th0 + 2 * d + j;
-          if (((rmask >> j) & 1) && tau < tend) {
-            Ltr = trace_event(Ltr, tau, RAFT_MSG_APPEND_RESPONSE, fk(j) + 1, Lterm, RAFT_LEADER,
-                              Lterm, 0);
-            rmask &= ~(1u << j);
-            Ldl = tau + S.hb;
-            ++nar;
-          }
-        }
-        if (rmask) whole = false;
-        else resA = INF;
-      }
-      if (whole) fixed_point_rounds(mid ? th0 + P : th0);
+      run_launch(fx, mid, th0, tend, d, S.hb, S.el_base, P, bs);
     }
 #ifdef RS_WAVELOG
-    asm volatile("" ::"v"(Ltr), "v"(ftr[0]), "v"(Ldl));
+    asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
     wl_x3 = wall_clock64();                     // the fixed-point path's rounds done
 #endif
 #ifdef RS_WAVELOG
@@ -1458,8 +1331,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       for (;;) {
         uint32_t due = 0;
 #pragma unroll
-        for (int j = 0; j < F; ++j) due |= (uint32_t)(fdl[j] <= t) << j;
-        due &= fpend;
+        for (int j = 0; j < F; ++j) due |= (uint32_t)(fx.fdl[j] <= t) << j;
+        due &= fx.fpend;
         if (!run || t >= tend || !due) break;
         draw_deadlines(due);
         t = max(tn, next_event());
@@ -1473,41 +1346,41 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       RS_LPH(0);
       if (!on) continue;
       // ------------------------------------------------ decide on the pre-tick state
-      const bool lres = rmask != 0 && resA <= t;               // a message beats the deadline
-      const bool lhb = !lres && Ldl <= t;
+      const bool lres = fx.rmask != 0 && fx.resA <= t;               // a message beats the deadline
+      const bool lhb = !lres && fx.Ldl <= t;
       uint32_t fae = 0, fto = 0;
 #pragma unroll
       for (int j = 0; j < F; ++j) {
-        const bool a = qA[j] <= t;
+        const bool a = fx.qA[j] <= t;
         fae |= (uint32_t)a << j;
-        fto |= (uint32_t)(!a && fdl[j] <= t) << j;
+        fto |= (uint32_t)(!a && fx.fdl[j] <= t) << j;
       }
       bool bail = fto != 0;                                    // a follower's election timeout
       if (lhb) {
-        bail = bail || qmask != 0;                             // a follower still holds one
+        bail = bail || fx.qmask != 0;                             // a follower still holds one
 #pragma unroll
         for (int j = 0; j < F; ++j) {
           const uint32_t pv = nx[j] - 1 > 0 ? (uint32_t)(nx[j] - 1) : 0u;
           bail = bail || pv < Llen || pv >= (1u << 24);        // entries to ship
         }
       }
-      const int hs = __builtin_ctz(rmask | (1u << F));
+      const int hs = __builtin_ctz(fx.rmask | (1u << F));
       uint32_t xT = 0, xH = 0;
 #pragma unroll
       for (int j = 0; j < F; ++j) {
         if (j == hs) {
-          xT = rT[j]; xH = rH[j];
+          xT = fx.rT[j]; xH = fx.rH[j];
         }
       }
       const uint32_t xid = (uint32_t)hs + 1 + ((uint32_t)hs >= L ? 1u : 0u);
       if (lres)
         bail = bail || xT > Lterm || (xH ? ackbad : ((Lmk >> (16 + xid)) & 1) == 0);
       if (fae) {
-        bail = bail || rmask != 0;                             // responses of two ticks
+        bail = bail || fx.rmask != 0;                             // responses of two ticks
 #pragma unroll
         for (int j = 0; j < F; ++j)
           if ((fae >> j) & 1)
-            bail = bail || qb[j] != 0 || !(qT[j] < fterm[j] || flen[j] <= fcommit[j]);
+            bail = bail || fx.qb[j] != 0 || !(fx.qT[j] < fterm[j] || flen[j] <= fcommit[j]);
       }
       RS_LPH(1);
       if (bail) {                              // the general tick body runs this tick
@@ -1522,13 +1395,13 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       if (lhb) {                               // heartbeat-handler: empty append-entries to all
 #pragma unroll
         for (int j = 0; j < F; ++j) {
-          qA[j] = t + d; qT[j] = Lterm; qa[j] = Lcommit;
-          qb[j] = nx[j] - 1 > 0 ? (uint32_t)(nx[j] - 1) : 0u;
+          fx.qA[j] = t + d; fx.qT[j] = Lterm; fx.qa[j] = Lcommit;
+          fx.qb[j] = nx[j] - 1 > 0 ? (uint32_t)(nx[j] - 1) : 0u;
         }
-        qmask = (1u << F) - 1;
-        Ldl = t + S.hb;
-        Ltr = trace_event(Ltr, t, 7, 0, 0, RAFT_LEADER, Lterm, 0);
-        ++nhb;
+        fx.qmask = (1u << F) - 1;
+        fx.Ldl = t + S.hb;
+        fx.Ltr = trace_event(fx.Ltr, t, 7, 0, 0, RAFT_LEADER, Lterm, 0);
+        ++fx.nhb;
         // The whole heartbeat round in this trip when nothing else can happen before its last
         // response: every follower takes the append-entries at t + d (no follower deadline before
         // it; the handler's checks pass), the followers' re-armed deadlines (>= t + d + el_base) and
@@ -1537,10 +1410,11 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         // responses then run in slot order up to the launch end (the rest stay queued) and stop at
         // one outside the model (the next trip decides it). A deferred deadline counts with its
         // lower bound here (a round not taken is run tick by tick).
-        round = rmask == 0 && S.hb >= 2 * d + F && S.el_base >= d + F && tend - t > d;
+        round = fx.rmask == 0 && S.hb >= 2 * d + F && S.el_base >= d + F && tend - t > d;
 #pragma unroll
         for (int j = 0; j < F; ++j)
-          round = round && fdl[j] >= t + d && qb[j] == 0 && (Lterm < fterm[j] || flen[j] <= fcommit[j]);
+          round = round && fx.fdl[j] >= t + d && fx.qb[j] == 0 &&
+                  (Lterm < fterm[j] || flen[j] <= fcommit[j]);
       }
       RS_LPH(2);
       // A trip runs exactly one of: a whole round (below), a heartbeat alone (its round did not fit:
@@ -1551,13 +1425,14 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
         for (int j = 0; j < F; ++j) {
           if ((fa >> j) & 1) {
-            const uint32_t mterm = qT[j], rterm = fterm[j];
+            const uint32_t mterm = fx.qT[j], rterm = fterm[j];
             const bool ok = mterm >= fterm[j];
             const uint32_t nfl2 = ok ? (ffl[j] & ~FL_FOLLOW) |
                                            pack_flags(RAFT_FOLLWER, 0, Lid, 0, 0, 0)
                                      : ffl[j];
             const uint32_t nterm = ok ? mterm : fterm[j];
-            ftr[j] = trace_event(ftr[j], ta, RAFT_MSG_APPEND_ENTRIES, Lid, mterm, fl_role(nfl2), nterm, 0);
+            fx.ftr[j] = trace_event(fx.ftr[j], ta, RAFT_MSG_APPEND_ENTRIES, Lid, mterm, fl_role(nfl2),
+                                    nterm, 0);
             if (ok) {
               fcommit[j] = flen[j];                            // apply-entries! (nothing applied)
               fmk[j] &= 0xFFFF0000u;
@@ -1565,16 +1440,16 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
             fterm[j] = nterm;
             ffl[j] = nfl2;
             // the response: to the leader's RES queue, in sender id order
-            rT[j] = rterm; rA[j] = ok ? qa[j] : 0u; rB[j] = 0; rH[j] = ok;
-            qA[j] = INF;
-            fdl[j] = ta + S.el_base;                           // + the deferred draw
+            fx.rT[j] = rterm; fx.rA[j] = ok ? fx.qa[j] : 0u; fx.rB[j] = 0; fx.rH[j] = ok;
+            fx.qA[j] = INF;
+            fx.fdl[j] = ta + S.el_base;                           // + the deferred draw
           }
         }
-        fpend |= fa;
-        qmask &= ~fa;
-        rmask = fa;
-        resA = ta + d;
-        nae += __popc(fa);
+        fx.fpend |= fa;
+        fx.qmask &= ~fa;
+        fx.rmask = fa;
+        fx.resA = ta + d;
+        fx.nae += __popc(fa);
         tl = ta;
       };
       // append-response-handler for follower slot j's response at tick tau (core.clj:141-149);
@@ -1582,15 +1457,15 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       // that would be checker work, or a failure without the peer's key (NPE)
       auto response = [&](int j, uint32_t tau, uint32_t yT, uint32_t yA, uint32_t yB, uint32_t yH,
                           int32_t& nxj, int32_t& mtj) {
-        const uint32_t yid = fk(j) + 1;
+        const uint32_t yid = fx.fk(j) + 1;
         if (yT > Lterm || (yH ? ackbad : ((Lmk >> (16 + yid)) & 1) == 0)) return false;
-        rmask &= ~(1u << j);
+        fx.rmask &= ~(1u << j);
         Lmk |= yH << (16 + yid);
         nxj = yH ? (int32_t)yB : nxj - 1;
         mtj = yH ? (int32_t)yA : mtj;
-        Ldl = tau + S.hb;
-        Ltr = trace_event(Ltr, tau, RAFT_MSG_APPEND_RESPONSE, yid, yT, RAFT_LEADER, Lterm, 0);
-        ++nar;
+        fx.Ldl = tau + S.hb;
+        fx.Ltr = trace_event(fx.Ltr, tau, RAFT_MSG_APPEND_RESPONSE, yid, yT, RAFT_LEADER, Lterm, 0);
+        ++fx.nar;
         tl = tau;
         return true;
       };
@@ -1603,8 +1478,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
         for (int j = 0; j < F; ++j)     // (a round cut by the launch end leaves the rest queued)
           go = go && t + 2 * d + j < tend &&
-               response(j, t + 2 * d + j, rT[j], rA[j], rB[j], rH[j], nx[j], mt[j]);
-        if (!rmask) resA = INF;
+               response(j, t + 2 * d + j, fx.rT[j], fx.rA[j], fx.rB[j], fx.rH[j], nx[j], mt[j]);
+        if (!fx.rmask) fx.resA = INF;
         if (at_fixed_point()) {
           fixed_point_rounds(t + P);
           tl = tend - 1;                       // nothing of the cluster is left before tend
@@ -1619,20 +1494,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         uint32_t tau0 = t;
         if (fae) {
           append_entries(t, fae);
-          tau0 = Ldl >= t + d ? t + d : tend;
+          tau0 = fx.Ldl >= t + d ? t + d : tend;
         }
         uint32_t E = tend;
 #pragma unroll
-        for (int j = 0; j < F; ++j) E = min(E, min(fdl[j], qA[j]));
+        for (int j = 0; j < F; ++j) E = min(E, min(fx.fdl[j], fx.qA[j]));
         if (lres) E = max(E, t + 1);
-        for (uint32_t tau = tau0; rmask && tau < E; ++tau) {
-          const int h2 = __builtin_ctz(rmask);
+        for (uint32_t tau = tau0; fx.rmask && tau < E; ++tau) {
+          const int h2 = __builtin_ctz(fx.rmask);
           bool ok = true;
 #pragma unroll
           for (int j = 0; j < F; ++j)
-            if (j == h2) ok = response(j, tau, rT[j], rA[j], rB[j], rH[j], nx[j], mt[j]);
+            if (j == h2) ok = response(j, tau, fx.rT[j], fx.rA[j], fx.rB[j], fx.rH[j], nx[j], mt[j]);
           if (!ok) break;
-          if (!rmask) resA = INF;
+          if (!fx.rmask) fx.resA = INF;
         }
         // The round finished here need not be on the period-P schedule. Responses that waited
         // behind the leader's other events (an election's vote responses, one per tick), or a
@@ -1642,14 +1517,15 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         // only if every follower's deadline (its lower bound, where the draw is owed) holds until
         // that append-entries arrives (a tie: the message wins, SIM_SPEC P1) or to the launch's
         // end; otherwise it is run tick by tick.
-        bool quiet = at_fixed_point() && Ldl > tl;
+        bool quiet = at_fixed_point() && fx.Ldl > tl;
         {
-          const uint32_t nxt = (uint32_t)min((uint64_t)Ldl + d, (uint64_t)tend);   // the next AE (or the end)
+          // the next AE (or the end)
+          const uint32_t nxt = (uint32_t)min((uint64_t)fx.Ldl + d, (uint64_t)tend);
 #pragma unroll
-          for (int j = 0; j < F; ++j) quiet = quiet && fdl[j] >= nxt;
+          for (int j = 0; j < F; ++j) quiet = quiet && fx.fdl[j] >= nxt;
         }
         if (quiet) {
-          fixed_point_rounds(Ldl);
+          fixed_point_rounds(fx.Ldl);
           tl = tend - 1;
         }
       }
@@ -1680,34 +1556,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     // (a cluster that ran its election here changed flags, masks and terms too)
     const bool wfp = !__builtin_amdgcn_ballot_w64(wb && (!fp || el));
     if (wb) {
-      // every word of fields DEADLINE..LEN, from registers (LEN unchanged)
+      // every word of fields DEADLINE..LEN, from registers (LEN unchanged): fx's, and beside them
+      // the fields only this path holds
       constexpr int NV = HF_NEXT;
       uint32_t v[NV][N];
 #pragma unroll
       for (int k = 0; k < N; ++k) {
-        // node k is the leader (k == L) or follower slot k - 1 (k > L) / k (k < L)
         const bool isL = (uint32_t)k == L;
-        const int jl = k > 0 ? k - 1 : 0, jh = k < F ? k : F - 1;
-        const bool lo = (uint32_t)k > L;
-        auto fv = [&](const uint32_t* x) { return msel(lo, x[jl], x[jh]); };
-        const uint32_t fq = (qmask >> (lo ? jl : jh)) & 1;
-        const uint32_t fqa = fv(qA);
-        const uint64_t trf = (uint64_t)msel(lo, (uint32_t)(ftr[jl] >> 32), (uint32_t)(ftr[jh] >> 32)) << 32 |
-                            msel(lo, (uint32_t)ftr[jl], (uint32_t)ftr[jh]);
-        const uint64_t tr = isL ? Ltr : trf;
-        v[HF_FLAGS][k] = isL ? Lfl : (fv(ffl) & ~FL_DRAW) | (((fpend >> (lo ? jl : jh)) & 1) ? FL_DRAW : 0u);
-        v[HF_MASKS][k] = isL ? Lmk : fv(fmk);
-        v[HF_TERM][k] = isL ? Lterm : fv(fterm);
-        v[HF_COMMIT][k] = isL ? Lcommit : fv(fcommit);
-        v[HF_LEN][k] = isL ? Llen : fv(flen);
-        v[HF_DEADLINE][k] = isL ? Ldl : fv(fdl);
-        v[HF_QMETA][k] = isL ? pack_qmeta(0, 0, 0, __popc(rmask)) : pack_qmeta(0, fq, 0, 0);
-        v[HF_REQ_ARR][k] = isL ? INF : (fq ? fqa : INF);
-        v[HF_RES_ARR][k] = isL ? resA : INF;
-        v[HF_REQ_TAIL][k] = isL ? 0u : (fq ? fqa : 0u);
-        v[HF_RES_TAIL][k] = isL ? (rmask ? resA : 0u) : 0u;
-        v[HF_TRACE_LO][k] = (uint32_t)tr;
-        v[HF_TRACE_HI][k] = (uint32_t)(tr >> 32);
+        fx.node_words(k, v);
+        v[HF_FLAGS][k] = isL ? Lfl : (fx.at_node(ffl, k) & ~FL_DRAW) |
+                                         (((fx.fpend >> fx.slot(k)) & 1) ? FL_DRAW : 0u);
+        v[HF_MASKS][k] = isL ? Lmk : fx.at_node(fmk, k);
+        v[HF_TERM][k] = isL ? Lterm : fx.at_node(fterm, k);
+        v[HF_COMMIT][k] = isL ? Lcommit : fx.at_node(fcommit, k);
+        v[HF_LEN][k] = isL ? Llen : fx.at_node(flen, k);
       }
       auto live = [](int q) { return q >= (int)HOT_CW && q < (int)(HOT_CW + HF_NEXT * N); };
       auto val = [&](int q) { return v[(q - HOT_CW) / N][(q - HOT_CW) % N]; };
@@ -1752,8 +1614,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       if (!wfp) {
 #pragma unroll
         for (int j = 0; j < F; ++j) {
-          const uint32_t qn = HOT_CW + (HF_NEXT + fk(j)) * N + L;
-          const uint32_t qt = HOT_CW + (HF_NEXT + N + fk(j)) * N + L;
+          const uint32_t qn = HOT_CW + (HF_NEXT + fx.fk(j)) * N + L;
+          const uint32_t qt = HOT_CW + (HF_NEXT + N + fx.fk(j)) * N + L;
           if (nx[j] != nx0[j]) {
             *lds_at<uint32_t>(img, img_off(lane, qn / 4) + 4 * (qn % 4)) = (uint32_t)nx[j];
             dl |= 1u << (qn / 32);
@@ -1765,29 +1627,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         }
       }
     }
-    // queues back to the rings, heads at slot 0 (a message in flight at the launch's end: rare)
-    if (__builtin_amdgcn_ballot_w64(wb && (qmask || rmask))) {            // wave-uniform
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        if (wb && ((qmask >> j) & 1)) {
-          uint4* dp = reinterpret_cast<uint4*>(qslots(S, c * N + fk(j), 0));
-          dp[0] = make_uint4(qA[j], RAFT_MSG_APPEND_ENTRIES | Lid << 3, qT[j], qa[j]);
-          dp[1] = make_uint4(qb[j], 0, 0, 0);
-        }
-      }
-      uint4* rp = reinterpret_cast<uint4*>(qslots(S, c * N + L, 1));
-      uint32_t n = 0;
-#pragma unroll
-      for (int j = 0; j < F; ++j) {
-        if (wb && ((rmask >> j) & 1)) {
-          const uint32_t sid = fk(j) + 1;
-          uint4* dp = rp + 2 * n;
-          dp[0] = make_uint4(resA, RAFT_MSG_APPEND_RESPONSE | sid << 3 | rH[j] << 7, rT[j], rA[j]);
-          dp[1] = make_uint4(rB[j], 0, 0, 0);
-          ++n;
-        }
-      }
-    }
+    fx.to_rings(S, c, wb);
+    nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
   }   // the general path
   // Dirty lines back to memory whole: a wave instruction writes eight clusters' line (8 lanes x
   // 16 B each), read from the image (line ln of cluster cc is its chunks 8 ln .. 8 ln + 7): the

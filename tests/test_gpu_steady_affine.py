@@ -1,4 +1,4 @@
-"""The steady kernel's affine step (csrc/fixed_point_affine.hpp, FixedPoint::rounds): a launch's K
+"""The steady kernel's affine step (csrc/fixed_point_affine.hpp, rs::rounds): a launch's K
 whole heartbeat rounds as one multiply-add per trace hash, for the two values of K a launch holds
 for clusters on the schedule, and the loop over rounds for every other K. After every launch the
 GPU is compared with the C oracle: digests, counters and every node record."""

@@ -99,6 +99,39 @@ def test_host_written_ties(nodes, d, monkeypatch):
             r.close()
 
 
+REWRITTEN = (0, 64, 128, 192)      # the first cluster of each wave of the 199
+
+
+@pytest.mark.parametrize("nodes", [2, 5])
+def test_general_path_round_in_progress(nodes, monkeypatch):
+    """The general path's fixed-point branch with a round in progress at t0 (append-entries in
+    flight, responses cut), at `corner` with d = 1. Before every launch the host rewrites one
+    settled cluster of each wave with the node records just read from it: the write changes nothing
+    the oracle can see and clears the cluster's certificate, so every wave loads all its lines and
+    takes the general path, where the rewritten cluster is at the fixed point in whatever phase of
+    its round the launch starts. (A read resolves a deferred draw and the write stores the exact
+    deadline: test_gpu_steady_line0's nodes_same, the same state to the oracle.) After the
+    elections and a launch of 2P ticks: 2P + 2 single-tick launches, then launches of P - 1, P + 1
+    and 3P + 1 ticks. No launch may bail more clusters than the oracle shows unsettled before it,
+    within the corner bound of test_threshold_schedule: a rewritten cluster that bailed for a
+    threshold of this branch would still compare equal."""
+    set_mode(monkeypatch, "always")
+    cfg, P = se.edge_cfg(nodes, 1, "corner")
+    g, r = pair(cfg)
+    launch(g, r, 300 * P, "election launch", "always")
+    launch(g, r, 2 * P, f"launch of {2 * P}", "always")
+    for i, nt in enumerate([1] * (2 * P + 2) + [P - 1, P + 1, 3 * P + 1]):
+        unsettled = se.settled(r)[0]
+        for c in REWRITTEN:
+            se.leader_of(r, c)                   # settled: at the fixed point, in some phase
+            for be in (g, r):
+                be.write_nodes(c, be.read_nodes_raw(c, 1))
+        launch(g, r, nt, f"launch {i} of {nt}", "always")
+        bails = g.diag_last_bails()
+        print(f"N={nodes} launch {i} of {nt}: bails {bails}, oracle unsettled {unsettled} before it")
+        assert bails <= unsettled + se.C_EDGE // 16, (i, nt)
+
+
 @pytest.mark.parametrize("variant", ["Q2F", "Q2F-1"])
 @pytest.mark.parametrize("d", [1, 2])
 @pytest.mark.parametrize("nodes", [2, 3, 4, 5])

@@ -1,6 +1,6 @@
 """The line-0 body in node order (steady_kernel.hip, NodeOrder): a wave under strong certificates
 keeps its clusters' hashes and deadlines by node, not by follower slot, and what the followers share
-as one value each. A wrong node/slot mapping shows only for some leader positions, so the configs
+as one value each (rs::run_launch and rs::rounds run on it as on FixedPoint). A wrong node/slot mapping shows only for some leader positions, so the configs
 here are checked to put a leader in every position. Everything compares the GPU with the C oracle
 after every launch: digests, counters, every node record."""
 import numpy as np
