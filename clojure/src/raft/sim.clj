@@ -230,6 +230,60 @@
                       :len-max (.getInt m (+ b 24))
                       :queued (.getInt m (+ b 28))}))}))
 
+;; raft_audit_t (136 bytes, 17 u64): clusters 0, by_class[8] 8, then eight scalars from 72.
+;; No reference counterpart: whether the nodes' logs agree as they stand, read on the device.
+(def audit-size 136)
+(def audit-classes
+  {:diverged 1 :commit-diverged 2 :match-broken 4 :term-order 8 :identical 16})
+(def ^:private audit-class-order
+  [:diverged :commit-diverged :match-broken :term-order :identical])
+(def ^:private audit-scalars
+  [:entries :agree-sum :agree-min :agree-max :diverged-nodes :commit-diverged-nodes
+   :diverge-index-min :commit-diverge-index-min])
+
+(defn audit
+  "The log audit of every cluster of the handle (raft_audit_read): :by-class maps each class of
+  audit-classes to its number of clusters, :entries is the sum of all log lengths, :agree-* the
+  common prefix of a cluster's logs over the clusters, :*-nodes the nodes in a diverging pair and
+  :*-index-min the first diverging position anywhere (-1, UINT64_MAX, when there is none)."
+  [sim]
+  (let [m (Memory. audit-size)
+        a64s (fn [off cnt] (vec (for [i (range cnt)] (.getLong m (+ off (* 8 i))))))]
+    (call "raft_audit_read" (:ptr sim) m)
+    (merge {:clusters (.getLong m 0)
+            :by-class (zipmap audit-class-order (a64s 8 5))}
+           (zipmap audit-scalars (a64s 72 8)))))
+
+;; raft_audit_record_t (32 bytes): cluster 0, classes 4, agree_len 8, diverge_index 12,
+;; commit_diverge_index 16, order_index 20 (an index of -1, UINT32_MAX: none), diverged 24 and
+;; commit_diverged 26 (u16 masks, bit i = id i), len_min 28.
+(def audit-record-size 32)
+
+(defn audit-select
+  "The clusters in given audit classes, in ascending cluster order (raft_audit_select): {:total n
+  :records [...]}, with the predicate of select-clusters over the keys of audit-classes. At most
+  `cap` records are copied (cap 0: the total alone); the selection runs on the device."
+  [sim any all none cap]
+  (let [mask (fn [ks] (int (reduce bit-or 0 (map audit-classes ks))))
+        m (Memory. (* audit-record-size (max 1 cap)))
+        total (.invokeLong (f "raft_audit_select")
+                           (object-array [(:ptr sim) (mask any) (mask all) (mask none)
+                                          (when (pos? cap) m) (int cap)]))
+        ids (fn [bits] (set (filter #(bit-test bits %) (range 1 (inc (:nodes sim))))))]
+    (when (neg? total) (throw (ex-info (last-error) {:rc total})))
+    {:total total
+     :records (vec (for [i (range (min total cap)) :let [r (* i audit-record-size)]]
+                     {:cluster (.getInt m r)
+                      :classes (set (for [[k bit] audit-classes
+                                          :when (pos? (bit-and bit (.getInt m (+ r 4))))] k))
+                      :agree-len (.getInt m (+ r 8))
+                      :diverge-index (.getInt m (+ r 12))
+                      :commit-diverge-index (.getInt m (+ r 16))
+                      :order-index (.getInt m (+ r 20))
+                      :diverged (ids (.getShort m (+ r 24)))
+                      :commit-diverged (ids (.getShort m (+ r 26)))
+                      :len-min (.getInt m (+ r 28))}))}))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

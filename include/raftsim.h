@@ -346,6 +346,61 @@ int raft_census_read(raft_sim_t* sim, raft_census_t* out);
 int64_t raft_census_select(raft_sim_t* sim, uint32_t any_mask, uint32_t all_mask,
                            uint32_t none_mask, raft_cluster_state_t* out, uint32_t cap);
 
+/* ---- Log audit (no reference counterpart, none in the oracle) -------------------------------
+ * Whether the nodes' logs agree right now, answered on the device from the log contents as they
+ * stand (the entries raft_sim_read_arena would copy, every node of every cluster), without copying
+ * them: State Machine Safety and Log Matching read off the state, not counted when they happened.
+ * Node k's log is its log_len entries, entry p the (term, val) at arena slot (arena_base + p) mod
+ * arena_cap; halted nodes count. For a pair i < j, m = min(len_i, len_j) and d_ij is the smallest
+ * p < m at which the two entries differ in term or val, or m (SIM_SPEC.md, "Derived, not state"). */
+enum raft_audit_class {
+  RAFT_AUD_DIVERGED = 1,        /* some pair has d_ij < m */
+  RAFT_AUD_COMMIT_DIVERGED = 2, /* some pair has d_ij < m and d_ij < min(commit_i, commit_j) */
+  RAFT_AUD_MATCH_BROKEN = 4,    /* some pair has a p, d_ij <= p < m, with term_i[p] == term_j[p] */
+  RAFT_AUD_TERM_ORDER = 8,      /* some node has term[p] > term[p + 1], p + 1 < len */
+  RAFT_AUD_IDENTICAL = 16       /* no pair diverges and all N lengths are equal */
+};
+#define RAFT_AUD_ALL 31
+
+typedef struct raft_audit {             /* every field uint64_t */
+  uint64_t clusters;
+  uint64_t by_class[8];                 /* clusters with class bit b set; b >= 5: 0 */
+  uint64_t entries;                     /* sum of log_len over all nodes */
+  uint64_t agree_sum, agree_min, agree_max; /* agree_len over the clusters */
+  uint64_t diverged_nodes, commit_diverged_nodes; /* popcounts of the records' masks, summed */
+  uint64_t diverge_index_min, commit_diverge_index_min; /* UINT64_MAX when no cluster has one */
+} raft_audit_t;
+
+typedef struct raft_audit_record {      /* 32 bytes */
+  uint32_t cluster;                     /* handle-local, as raft_sim_read_nodes takes it */
+  uint32_t classes;                     /* raft_audit_class bits */
+  uint32_t agree_len;                   /* the common prefix of all N logs: min over pairs of d_ij */
+  uint32_t diverge_index;               /* min d_ij over diverging pairs; UINT32_MAX: none */
+  uint32_t commit_diverge_index;        /* min d_ij over the pairs of bit 2; UINT32_MAX: none */
+  uint32_t order_index;                 /* the smallest p of bit 8 in any node; UINT32_MAX: none */
+  uint16_t diverged, commit_diverged;   /* bit i: id i is in a pair of bit 1 / bit 2 (as votes) */
+  uint32_t len_min;                     /* the shortest log */
+} raft_audit_record_t;
+
+/* The audit of every cluster of the handle, reduced over its devices (sums; MIN of agree_min and
+ * the *_index_min fields; MAX of agree_max). Both calls run on the device, stream-ordered after
+ * everything enqueued (valid after raft_sim_step_async, which they wait for), read the state only
+ * (digest, counters, violation records and a steady certificate stay), and give bitwise the same
+ * answer for the same state. The per-cluster records a query computes stay valid until the next
+ * raft_sim_step, raft_sim_step_async, raft_sim_write_nodes, raft_sim_write_arena or
+ * raft_sim_write_clusters: queries in between read the records, not the logs again. -EINVAL: null
+ * argument; -EIO: a HIP error, or a handle poisoned by a failed step. */
+int raft_audit_read(raft_sim_t* sim, raft_audit_t* out);
+
+/* The clusters whose class word satisfies the predicate of raft_census_select over
+ * raft_audit_class bits, in ascending cluster order: the first min(total, cap) records are written
+ * to out (which may be null when cap is 0: count only). Returns the number of matching clusters,
+ * which may exceed cap, or a negative errno (-EINVAL: a mask above RAFT_AUD_ALL, all_mask &
+ * none_mask nonzero, null out with cap > 0, null sim: refused before any device is touched; -EIO
+ * as above). */
+int64_t raft_audit_select(raft_sim_t* sim, uint32_t any_mask, uint32_t all_mask,
+                          uint32_t none_mask, raft_audit_record_t* out, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

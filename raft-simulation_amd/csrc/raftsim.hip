@@ -35,6 +35,17 @@ hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream
 hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
                                 unsigned long long* scratch, void* out, uint32_t cap,
                                 hipStream_t st);
+// audit_kernel.hip
+size_t audit_scratch_words(uint32_t C);
+size_t audit_result_word(uint32_t C);
+const uint32_t* audit_total_ptr(unsigned long long* scratch, uint32_t C);
+void audit_init(raft_audit_t* acc);
+void audit_combine(raft_audit_t* acc, const raft_audit_t* x);
+hipError_t launch_audit(const DevSim& S, uint32_t width, void* rec, unsigned long long* scratch,
+                        hipStream_t st);
+hipError_t launch_audit_select(uint32_t C, uint32_t any, uint32_t all, uint32_t none,
+                               const void* rec, unsigned long long* scratch, void* out,
+                               uint32_t cap, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -120,6 +131,16 @@ struct Shard {
   double viol_ms;
   unsigned long long* cscratch;
   double census_ms;
+  // raft_audit_read / raft_audit_select (audit_kernel.hip): the per-cluster records and the
+  // scratch (partial and folded summaries, the compaction's counts), made by the first query, and
+  // the last query's device time (raftsim_diag_audit_ms). audit_valid: the records and the folded
+  // summary are those of the state as it stands; every call that can change a log or a commit
+  // index clears it (steps, raft_sim_write_nodes / _arena / _clusters), so queries in between
+  // walk the arenas once.
+  raft_audit_record_t* arec;
+  unsigned long long* ascratch;
+  bool audit_valid;
+  double audit_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
 // The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
@@ -361,6 +382,7 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
 // Enqueue n_ticks on the shard's stream. s->tick advances launch by launch, so after a failure it
 // still names the tick the state has reached (the handle is then poisoned anyway).
 static int sh_step_async(Shard* s, uint32_t n_ticks) {
+  s->audit_valid = false;
   HIP_OK(hipSetDevice(s->cfg.device));
   uint32_t launches = s->pending_launches;
   if (!s->pending) {
@@ -568,6 +590,7 @@ static int sh_write_nodes(Shard* s, uint32_t c0, uint32_t nc, const raft_node_t*
   int rc = check_range(s, c0, nc);
   if (rc) return rc;
   s->storm_until = 0;
+  s->audit_valid = false;
   if (!in) return fail(-EINVAL, "null input");
   HIP_OK(hipSetDevice(s->cfg.device));
   const uint32_t N = s->N, all = ((1u << (N + 1)) - 1) & ~1u;
@@ -693,6 +716,7 @@ static int sh_write_arena(Shard* s, uint32_t cluster, uint32_t id, const raft_en
   int rc = check_node(s, cluster, id);
   if (!rc) s->storm_until = 0;
   if (rc) return rc;
+  s->audit_valid = false;
   if (count > s->A || (count && !in)) return fail(-EINVAL, "count > arena_cap");
   HIP_OK(hipSetDevice(s->cfg.device));
   std::vector<raft_entry_t> buf(s->A);
@@ -807,6 +831,7 @@ static int sh_write_clusters(Shard* s, uint32_t c0, uint32_t nc, const raft_clus
   int rc = check_range(s, c0, nc);
   if (rc) return rc;
   s->storm_until = 0;
+  s->audit_valid = false;
   HIP_OK(hipSetDevice(s->cfg.device));
   std::vector<raft_cluster_t> buf(in, in + nc);
   for (auto& h : buf) {
@@ -1284,6 +1309,104 @@ extern "C" int raftsim_diag_census_ms(raft_sim_t* r, double* ms) {
   if (!r || !ms) return fail(-EINVAL, "null argument");
   double m = 0;
   for (Shard* s : r->sh) m = std::max(m, s->census_ms);
+  *ms = m;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Log audit (include/raftsim.h, "no reference counterpart, none in the oracle"): a read-only pass
+// over the hot blocks and the arenas on every shard's stream at once, behind whatever the shard
+// has enqueued. It leaves one record per cluster and the shard's summary on the device, valid
+// until the next call that can change a log or a commit index (Shard::audit_valid): the summary
+// is copied from there and folded over the shards on the host, selections compact the records
+// through sharded_query. Like the census it touches neither the state nor the host's bookkeeping
+// of it.
+static int audit_prepare(Shard* s) {
+  if (s->ascratch) return 0;
+  int rc = dalloc(s, &s->arec, s->C);
+  if (!rc) rc = dalloc(s, &s->ascratch, rs::audit_scratch_words(s->C));   // freed by sh_destroy
+  return rc;
+}
+// Enqueue the pass unless the shard's records are those of the state as it stands.
+static hipError_t audit_refresh(Shard* s) {
+  if (s->audit_valid) return hipSuccess;
+  // the pass's lanes per cluster (audit_kernel.hip; DESIGN.md has both widths' figures): 64 unless
+  // RAFTSIM_AUDIT_WIDTH=16 is in the environment. Same records and summary either way.
+  const char* aw = getenv("RAFTSIM_AUDIT_WIDTH");
+  const uint32_t width = aw && !strcmp(aw, "16") ? 16u : 64u;
+  const hipError_t e = rs::launch_audit(s->d, width, s->arec, s->ascratch, s->stream);
+  s->audit_valid = e == hipSuccess;
+  return e;
+}
+
+int raft_audit_read(raft_sim_t* r, raft_audit_t* out) {
+  if (!r || !out) return fail(-EINVAL, "null argument");
+  if (r->poisoned) return unusable();
+  const size_t G = r->sh.size();
+  std::vector<raft_audit_t> part(G);
+  int rc = 0;
+  auto step = [&](hipError_t e) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_audit_read: %s", hipGetErrorString(e));
+    return !rc;
+  };
+  size_t started = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    if (!step(hipSetDevice(s->cfg.device)) || (rc = audit_prepare(s))) break;
+    ++started;
+    step(hipEventRecord(s->qev0, s->stream)) && step(audit_refresh(s)) &&
+        step(hipEventRecord(s->qev1, s->stream)) &&
+        step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]),
+                 (const unsigned long long*)s->ascratch + rs::audit_result_word(s->C),
+                 sizeof(raft_audit_t) / 8));
+  }
+  rs::audit_init(out);
+  // every started shard is waited for, also after an error: its copy writes part[d]
+  for (size_t d = 0; d < started; ++d) {
+    Shard* s = r->sh[d];
+    float ms = 0;
+    step(hipSetDevice(s->cfg.device));
+    step(hipStreamSynchronize(s->stream));
+    if (rc) s->audit_valid = false;
+    if (rc || !step(hipEventElapsedTime(&ms, s->qev0, s->qev1))) continue;
+    s->audit_ms = ms;
+    rs::audit_combine(out, &part[d]);
+  }
+  return rc;
+}
+
+int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, uint32_t none_mask,
+                          raft_audit_record_t* out, uint32_t cap) {
+  if (!r) return fail(-EINVAL, "null sim");
+  if (any_mask > RAFT_AUD_ALL || all_mask > RAFT_AUD_ALL || none_mask > RAFT_AUD_ALL)
+    return fail(-EINVAL, "class masks must be <= RAFT_AUD_ALL (31)");
+  if (all_mask & none_mask) return fail(-EINVAL, "all_mask and none_mask share a class");
+  if (cap && !out) return fail(-EINVAL, "null output");
+  if (r->poisoned) return unusable();
+  const int64_t n = sharded_query(
+      r, cap, out, "raft_audit_select", audit_prepare,
+      [&](Shard* s, raft_audit_record_t* dout, uint32_t dcap, const uint32_t** dtotal) {
+        *dtotal = rs::audit_total_ptr(s->ascratch, s->C);
+        const hipError_t e = audit_refresh(s);
+        return e != hipSuccess ? e
+                               : rs::launch_audit_select(s->C, any_mask, all_mask, none_mask,
+                                                         s->arec, s->ascratch, dout, dcap,
+                                                         s->stream);
+      },
+      &Shard::audit_ms);
+  if (n < 0)
+    for (Shard* s : r->sh) s->audit_valid = false;
+  return n;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_audit_read's or
+// raft_audit_select's kernels (HIP events around them on each shard's stream), the maximum over
+// shards, in ms. A query that found the records valid ran no pass: its time is the copy's or the
+// compaction's alone.
+extern "C" int raftsim_diag_audit_ms(raft_sim_t* r, double* ms) {
+  if (!r || !ms) return fail(-EINVAL, "null argument");
+  double m = 0;
+  for (Shard* s : r->sh) m = std::max(m, s->audit_ms);
   *ms = m;
   return 0;
 }

@@ -208,6 +208,61 @@ _CENSUS_SIGS = {
 CENSUS_SYMBOLS = ["raft_census_" + n for n in _CENSUS_SIGS]
 
 
+# raft_audit_class bits (include/raftsim.h, "Log audit"; SIM_SPEC.md, "Derived, not state")
+AUDIT_CLASSES = {"diverged": 1, "commit_diverged": 2, "match_broken": 4, "term_order": 8,
+                 "identical": 16}
+AUD_ALL = 31
+_NONE32, _NONE64 = 2 ** 32 - 1, 2 ** 64 - 1
+
+
+class Audit(C.Structure):
+    """raft_audit_t: the log audit of a handle's clusters (no reference counterpart)."""
+    _fields_ = [("clusters", C.c_uint64), ("by_class", C.c_uint64 * 8), ("entries", C.c_uint64),
+                ("agree_sum", C.c_uint64), ("agree_min", C.c_uint64), ("agree_max", C.c_uint64),
+                ("diverged_nodes", C.c_uint64), ("commit_diverged_nodes", C.c_uint64),
+                ("diverge_index_min", C.c_uint64), ("commit_diverge_index_min", C.c_uint64)]
+
+    def as_dict(self):
+        d = {}
+        for f, t in self._fields_:               # the structure's order
+            v = getattr(self, f)
+            d[f] = int(v) if t is C.c_uint64 else [int(x) for x in v]
+        d["by_class"] = {k: d["by_class"][b.bit_length() - 1] for k, b in AUDIT_CLASSES.items()}
+        for f in ("diverge_index_min", "commit_diverge_index_min"):
+            d[f] = None if d[f] == _NONE64 else d[f]
+        return d
+
+
+class AuditRecord(C.Structure):
+    """raft_audit_record_t: one selected cluster (no reference counterpart)."""
+    _fields_ = [("cluster", C.c_uint32), ("classes", C.c_uint32), ("agree_len", C.c_uint32),
+                ("diverge_index", C.c_uint32), ("commit_diverge_index", C.c_uint32),
+                ("order_index", C.c_uint32), ("diverged", C.c_uint16),
+                ("commit_diverged", C.c_uint16), ("len_min", C.c_uint32)]
+
+    def as_dict(self, n_nodes, cluster_offset=0):
+        ids = range(1, n_nodes + 1)
+        idx = lambda v: None if v == _NONE32 else v  # noqa: E731
+        return {"cluster": self.cluster, "global_id": cluster_offset + self.cluster,
+                "classes": tuple(k for k, b in AUDIT_CLASSES.items() if self.classes & b),
+                "agree_len": self.agree_len, "diverge_index": idx(self.diverge_index),
+                "commit_diverge_index": idx(self.commit_diverge_index),
+                "order_index": idx(self.order_index),
+                "diverged": [i for i in ids if (self.diverged >> i) & 1],
+                "commit_diverged": [i for i in ids if (self.commit_diverged >> i) & 1],
+                "len_min": self.len_min}
+
+
+# The log audit, like the census, has no oracle counterpart: bound for the product library only,
+# under its own prefix.
+_AUDIT_SIGS = {
+    "read": (C.c_int, [C.c_void_p, P(Audit)]),
+    "select": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(AuditRecord),
+                           C.c_uint32]),
+}
+AUDIT_SYMBOLS = ["raft_audit_" + n for n in _AUDIT_SIGS]
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

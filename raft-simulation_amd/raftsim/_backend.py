@@ -275,12 +275,15 @@ class GpuBackend(Backend):
     """A handle of libraftsim.so: the ABI the oracle mirrors, plus the entry points it has no
     counterpart for (include/raftsim.h, "Violation records"): which clusters violated, which
     invariant, when first -- and the config that replays one of them alone; and ("State census")
-    what state the clusters are in now, counted and selected on the device."""
+    what state the clusters are in now, counted and selected on the device; and ("Log audit")
+    whether the nodes' logs agree as they stand, and whether they disagree below the commit
+    indices."""
 
     def __init__(self, lib_path, prefix, **config):
         super().__init__(lib_path, prefix, **config)
         self._viol = _abi.bind(self._lib, "raft_viol_", sigs=_abi._VIOL_SIGS)
         self._census = _abi.bind(self._lib, "raft_census_", sigs=_abi._CENSUS_SIGS)
+        self._audit = _abi.bind(self._lib, "raft_audit_", sigs=_abi._AUDIT_SIGS)
 
     def _viol_read(self, mask, t_lo, t_hi, cap):
         buf = (_abi.Violation * max(1, cap))()
@@ -394,6 +397,68 @@ class GpuBackend(Backend):
     def last_census_ms(self):
         """Diagnostic: device time (HIP events) of the last census() or select() query's kernels."""
         f = self._lib.raftsim_diag_census_ms
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        ms = C.c_double()
+        self._check(f(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- log audit (include/raftsim.h, "Log audit") ----------------------------------------------
+    def audit(self):
+        """Whether the nodes' logs agree right now, answered on the device from the arenas as they
+        stand (one pass over every log, nothing but the 136-byte result copied): a dict of
+        raft_audit_t's fields. `by_class` maps every class name (_abi.AUDIT_CLASSES; SIM_SPEC.md,
+        "Derived, not state") to the number of clusters in it: diverged (two logs differ at a
+        position both hold), commit_diverged (below both commit indices: State Machine Safety is
+        broken), match_broken (same index and term, yet not identical up to there), term_order (a
+        log's terms decrease somewhere), identical. `entries` is the sum of all log lengths,
+        agree_* the common prefix of a cluster's logs over the clusters, *_nodes the nodes that
+        belong to a diverging pair, *_index_min the first diverging position anywhere (None: no
+        cluster diverges). Stream-ordered: valid after step_async, which it waits for. Read-only.
+        The per-cluster records stay on the device until the next step or write of nodes, arenas or
+        clusters: an audit_select() after it reads them, not the logs again."""
+        a = _abi.Audit()
+        self._check(self._audit["read"](self._h, C.byref(a)))
+        return a.as_dict()
+
+    @staticmethod
+    def _audit_mask(names):
+        mask = 0
+        for k in names:
+            if k not in _abi.AUDIT_CLASSES:
+                raise ValueError(f"unknown audit class {k!r} (one of {list(_abi.AUDIT_CLASSES)})")
+            mask |= _abi.AUDIT_CLASSES[k]
+        return mask
+
+    def _audit_select(self, masks, cap):
+        buf = (_abi.AuditRecord * max(1, cap))()
+        n = int(self._audit["select"](self._h, *masks, buf if cap else None, cap))
+        return self._check(n), buf
+
+    def audit_select(self, any=(), all=(), none=(), limit=None):
+        """The clusters in given audit classes: (total, records), with the predicate and the
+        limit of select() over the names of _abi.AUDIT_CLASSES. A record is a dict: cluster
+        (handle-local, as read_nodes takes it), global_id, classes (the names of all the cluster's
+        classes), agree_len (the common prefix of its N logs), diverge_index /
+        commit_diverge_index (the first position at which two logs differ / differ below both
+        commit indices; None: nowhere), order_index (the first position whose term exceeds the
+        next one's; None), diverged / commit_diverged (the ids of the nodes in such a pair) and
+        len_min (the shortest log). The selection runs on the device; only the records asked for
+        are copied."""
+        masks = [self._audit_mask(x) for x in (any, all, none)]
+        if limit is None:
+            total, _ = self._audit_select(masks, 0)
+            cap = total
+        else:
+            cap = int(limit)
+        total, buf = self._audit_select(masks, cap)
+        off = self.config.cluster_offset
+        return total, [v.as_dict(self.N, off) for v in buf[:min(total, cap)]]
+
+    def last_audit_ms(self):
+        """Diagnostic: device time (HIP events) of the last audit() or audit_select() query's
+        kernels."""
+        f = self._lib.raftsim_diag_audit_ms
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         ms = C.c_double()

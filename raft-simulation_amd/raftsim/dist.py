@@ -72,6 +72,33 @@ def reduce_census(c: dict, device=None) -> dict:
     return {k: out[k] for k in c}
 
 
+def reduce_audit(a: dict, device=None) -> dict:
+    """All-reduce an audit dict (Simulator.audit()) over the default process group: SUM of the
+    counts and sums (the per-class counts element by element), MIN of agree_min and the
+    *_index_min fields (None: no cluster of the rank has one), MAX of agree_max."""
+    import torch
+    import torch.distributed as dist
+
+    mins = sorted(k for k in a if k.endswith("_min"))
+    maxes = sorted(k for k in a if k.endswith("_max"))
+    classes = list(a["by_class"])
+    sums = sorted(k for k in a if k not in mins and k not in maxes and k != "by_class")
+    v = torch.tensor([int(a[k]) for k in sums] + [int(a["by_class"][k]) for k in classes],
+                     dtype=torch.int64, device=device)
+    dist.all_reduce(v, op=dist.ReduceOp.SUM)
+    mx = torch.tensor([int(a[k]) for k in maxes], dtype=torch.int64, device=device)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    mn = torch.tensor([NONE_TICK if a[k] is None else int(a[k]) for k in mins],
+                      dtype=torch.int64, device=device)
+    dist.all_reduce(mn, op=dist.ReduceOp.MIN)
+    it = iter(int(x) for x in v.tolist())
+    out = {k: next(it) for k in sums}
+    out["by_class"] = {k: next(it) for k in classes}
+    out.update(zip(maxes, (int(x) for x in mx.tolist())))
+    out.update((k, None if x == NONE_TICK else x) for k, x in zip(mins, (int(x) for x in mn.tolist())))
+    return {k: out[k] for k in a}
+
+
 def reduce_max(x: float, device=None) -> float:
     import torch
     import torch.distributed as dist

@@ -16,7 +16,7 @@ while [ $# -ge 2 ]; do
     pids=("${pids[@]:1}")
   fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -DRS_DIAG_BUILD $2 \
-    -o "$R/raft-simulation_amd/build/libraftsim_$1.so" $C/tick_kernel.hip $C/steady_kernel.hip $C/storm_kernel.hip $C/violations_kernel.hip $C/census_kernel.hip $C/raftsim.hip &
+    -o "$R/raft-simulation_amd/build/libraftsim_$1.so" $C/tick_kernel.hip $C/steady_kernel.hip $C/storm_kernel.hip $C/violations_kernel.hip $C/census_kernel.hip $C/audit_kernel.hip $C/raftsim.hip &
   pids+=($!)
   shift 2
 done
