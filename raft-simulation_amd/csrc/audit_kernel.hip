@@ -24,49 +24,20 @@
 //     the last lane's of the step before (one rotation per node and step gives both).
 //
 // The pass writes one 32-byte record per cluster and, like the census, one partial summary per
-// workgroup that a second one-workgroup kernel folds: integer sums, minima and maxima, no atomics,
-// the launch boundary the only synchronisation, so the result depends on no arrival order. The
-// selection is the compaction of compact.hpp over the record buffer.
+// workgroup that a second one-workgroup kernel folds (summary.hpp: no atomics, the result depends
+// on no arrival order). The selection is the compaction of compact.hpp over the record buffer.
 #include <type_traits>
 
-#include "compact.hpp"
+#include "summary.hpp"
 
 namespace rs {
 
-constexpr uint32_t AUD_BLOCK = 256;                  // four waves
-constexpr uint32_t AUD_WAVES = AUD_BLOCK / 64;
-constexpr uint32_t AUD_MAX_GRID = 2048;              // workgroups (= partial summaries) at most
-constexpr uint32_t AUD_FOLD_BLOCK = 1024;            // the folding workgroup: 16 waves
-constexpr uint32_t AUD_NARROW = 16, AUD_WIDE = 64;   // the two group widths
-constexpr uint32_t AUD_F = sizeof(raft_audit_t) / 8; // u64 fields of a summary
-static_assert(sizeof(raft_audit_t) % 8 == 0 && AUD_F <= 64, "a summary is at most 64 u64 fields");
+constexpr uint32_t AUD_BLOCK = SUMMARY_BLOCK;        // four waves
+constexpr uint32_t AUD_WAVES = SUMMARY_WAVES;
+constexpr uint32_t AUD_F = summary_F<raft_audit_t>;  // u64 fields of a summary
 static_assert(sizeof(raft_audit_record_t) == 32, "raft_audit_record_t is eight words");
 
 #define AUD_IDX(field) ((uint32_t)(offsetof(raft_audit_t, field) / 8))
-
-// How field f of two summaries combines: 0 sum, 1 minimum, 2 maximum.
-__host__ __device__ inline int aud_op(uint32_t f) {
-  if (f == AUD_IDX(agree_min) || f == AUD_IDX(diverge_index_min) ||
-      f == AUD_IDX(commit_diverge_index_min))
-    return 1;
-  return f == AUD_IDX(agree_max) ? 2 : 0;
-}
-__host__ __device__ inline uint64_t aud_unit(uint32_t f) { return aud_op(f) == 1 ? ~0ull : 0ull; }
-__host__ __device__ inline uint64_t aud_fold(uint32_t f, uint64_t a, uint64_t b) {
-  const int op = aud_op(f);
-  return op == 0 ? a + b : op == 1 ? (a < b ? a : b) : (a > b ? a : b);
-}
-
-// Wave reduction of a lane value (all 64 lanes active), uniform result.
-__device__ __forceinline__ uint64_t aud_wave_fold(uint32_t f, uint64_t x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d);
-    x = aud_fold(f, x, (uint64_t)hi << 32 | lo);
-  }
-  return x;
-}
 
 // Shuffles of a pair mask inside a group of G lanes (32 bits hold the pairs up to N = 8).
 template <uint32_t G>
@@ -94,16 +65,6 @@ __device__ __forceinline__ uint64_t aud_shfl_xor(uint64_t x, int d) {
   return (uint64_t)aud_shfl_xor<G>((uint32_t)(x >> 32), d) << 32 | aud_shfl_xor<G>((uint32_t)x, d);
 }
 
-// The groups of 64 / G clusters a shard of C clusters has, and the pass's grid over them.
-__host__ __device__ inline uint32_t aud_groups(uint32_t C, uint32_t G) {
-  const uint32_t CPW = 64 / G;
-  return (C + CPW - 1) / CPW;
-}
-static uint32_t aud_grid(uint32_t C, uint32_t G) {
-  const uint32_t wg = (aud_groups(C, G) + AUD_WAVES - 1) / AUD_WAVES;
-  return wg < AUD_MAX_GRID ? wg : AUD_MAX_GRID;
-}
-
 // The audit pass: rec[c] = cluster c's record (two uint4), part[blockIdx.x] = the summary of the
 // clusters this workgroup strode over (AUD_F u64 fields). arena: [C * N][A] entries (term, val).
 template <uint32_t N, uint32_t G>
@@ -113,7 +74,6 @@ audit_kernel(const uint32_t* __restrict__ hot, uint32_t HB, const uint2* __restr
              unsigned long long* __restrict__ part) {
   constexpr uint32_t CPW = 64 / G, NP = N * (N - 1) / 2;
   using PM = typename std::conditional<(NP <= 32), uint32_t, uint64_t>::type;   // one bit per pair
-  __shared__ unsigned long long wrec[AUD_WAVES][AUD_F];
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t gl = lane & (G - 1), slot = lane / G, gbase = lane - gl;
   const uint32_t groups = aud_groups(C, G);
@@ -250,8 +210,7 @@ audit_kernel(const uint32_t* __restrict__ hot, uint32_t HB, const uint2* __restr
       cdiv_min = min(cdiv_min, cmin);
     }
   }
-  // the wave's summary: every lane takes part in the reductions, lane 0 stores. A 32-bit "none"
-  // (INF) widens to the summary's UINT64_MAX.
+  // the lane's summary: a 32-bit "none" (INF) widens to the summary's UINT64_MAX
   auto wide = [](uint32_t x) { return x == INF ? ~0ull : (uint64_t)x; };
   uint64_t x[AUD_F];
 #pragma unroll
@@ -267,43 +226,13 @@ audit_kernel(const uint32_t* __restrict__ hot, uint32_t HB, const uint2* __restr
   x[AUD_IDX(commit_diverged_nodes)] = n_cdiv;
   x[AUD_IDX(diverge_index_min)] = wide(div_min);
   x[AUD_IDX(commit_diverge_index_min)] = wide(cdiv_min);
-#pragma unroll
-  for (uint32_t f = 0; f < AUD_F; ++f) {
-    const uint64_t w = aud_wave_fold(f, x[f]);
-    if (lane == 0) wrec[wv][f] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < AUD_F) {
-    const uint32_t f = threadIdx.x;
-    uint64_t y = wrec[0][f];
-#pragma unroll
-    for (uint32_t w = 1; w < AUD_WAVES; ++w) y = aud_fold(f, y, wrec[w][f]);
-    part[(size_t)blockIdx.x * AUD_F + f] = y;
-  }
-}
-
-// One workgroup: out[0 .. AUD_F) = the np partial summaries folded field by field.
-__global__ void __launch_bounds__(AUD_FOLD_BLOCK)
-audit_fold_kernel(const unsigned long long* __restrict__ part, uint32_t np,
-                  unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long acc[AUD_FOLD_BLOCK / 64][64];
-  const uint32_t f = threadIdx.x & 63, row = threadIdx.x >> 6;
-  uint64_t x = aud_unit(f);
-  if (f < AUD_F)
-    for (uint32_t p = row; p < np; p += AUD_FOLD_BLOCK / 64)
-      x = aud_fold(f, x, part[(size_t)p * AUD_F + f]);
-  acc[row][f] = x;
-  __syncthreads();
-  if (threadIdx.x < AUD_F) {
-    for (uint32_t r = 1; r < AUD_FOLD_BLOCK / 64; ++r) x = aud_fold(f, x, acc[r][f]);
-    out[f] = x;
-  }
+  summary_block_store<raft_audit_t, 0>(nullptr, x, part);
 }
 
 // The selection's source for the compaction (compact.hpp): one record per lane, so the clusters
 // rise with (chunk, round, wave, lane). The counting pass uses the class word alone.
 struct aud_select {
-  static constexpr uint32_t ROUNDS = 4;
+  static constexpr uint32_t ROUNDS = AUD_ROUNDS;
   struct Item {
     uint4 a, b;
     bool act;
@@ -312,9 +241,7 @@ struct aud_select {
   uint32_t C, any, all, none;
   uint4* __restrict__ out;
 
-  __host__ __device__ uint32_t chunks() const {
-    return (C + ROUNDS * COMPACT_BLOCK - 1) / (ROUNDS * COMPACT_BLOCK);
-  }
+  __host__ __device__ uint32_t chunks() const { return aud_chunks(C); }
   __device__ __forceinline__ Item load(uint32_t b, uint32_t i) const {
     const uint32_t c = (b * ROUNDS + i) * COMPACT_BLOCK + threadIdx.x;   // < C + a chunk
     Item it;
@@ -327,8 +254,7 @@ struct aud_select {
     return it;
   }
   __device__ __forceinline__ bool match(const Item& it) const {
-    const uint32_t cls = it.a.y;
-    return it.act && (any == 0 || (cls & any) != 0) && (cls & all) == all && (cls & none) == 0;
+    return it.act && class_match(it.a.y, any, all, none);
   }
   __device__ __forceinline__ void gather(Item&) const {}
   __device__ __forceinline__ void store(const Item& it, uint32_t o) const {
@@ -337,44 +263,10 @@ struct aud_select {
   }
 };
 
-static uint32_t aud_chunks(uint32_t C) {
-  return aud_select{nullptr, C, 0, 0, 0, nullptr}.chunks();
-}
-
-// Partial summaries the scratch array holds: the larger of the two widths' grids. The wide groups
-// put one cluster on a wave, the narrow ones four, so the wide grid is the larger, up to four times.
-static uint32_t aud_parts(uint32_t C) {
-  const uint32_t a = aud_grid(C, AUD_NARROW), b = aud_grid(C, AUD_WIDE);
-  return a > b ? a : b;
-}
-// u64 words of the scratch array a shard's audit queries need: the pass's partial summaries and
-// the folded summary, then (as u32) the selection's compaction scratch.
-size_t audit_scratch_words(uint32_t C) {
-  return ((size_t)aud_parts(C) + 1) * AUD_F + (compact_scratch_words(aud_chunks(C)) + 1) / 2;
-}
-// Where the folded summary / the selection's total stand in the scratch array.
-size_t audit_result_word(uint32_t C) { return (size_t)aud_parts(C) * AUD_F; }
-static uint32_t* aud_counts(unsigned long long* scratch, uint32_t C) {
-  return reinterpret_cast<uint32_t*>(scratch + ((size_t)aud_parts(C) + 1) * AUD_F);
-}
-const uint32_t* audit_total_ptr(unsigned long long* scratch, uint32_t C) {
-  return compact_total_ptr(aud_counts(scratch, C), aud_chunks(C));
-}
-
-// acc <- acc folded with x, field by field (the host's reduction over shards).
-void audit_init(raft_audit_t* acc) {
-  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
-  for (uint32_t f = 0; f < AUD_F; ++f) a[f] = aud_unit(f);
-}
-void audit_combine(raft_audit_t* acc, const raft_audit_t* x) {
-  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
-  const uint64_t* b = reinterpret_cast<const uint64_t*>(x);
-  for (uint32_t f = 0; f < AUD_F; ++f) a[f] = aud_fold(f, a[f], b[f]);
-}
-
 template <uint32_t G>
-static void aud_launch(const DevSim& S, uint4* rec, unsigned long long* part, hipStream_t st) {
-  const dim3 grid(aud_grid(S.C, G)), block(AUD_BLOCK);
+static void aud_pass(const DevSim& S, uint4* rec, dim3 grid, unsigned long long* part,
+                     hipStream_t st) {
+  const dim3 block(AUD_BLOCK);
   const uint32_t* hot = S.hot;
   const uint2* arena = reinterpret_cast<const uint2*>(S.arena);
 #define AUD_CASE(n)                                                                            \
@@ -390,27 +282,28 @@ static void aud_launch(const DevSim& S, uint4* rec, unsigned long long* part, hi
 }
 
 // The audit pass over shard S with groups of `width` lanes (64, or 16): rec (S.C records) receives
-// every cluster's record with shard-local cluster indices, scratch[audit_result_word(C) ...] the
-// shard's raft_audit_t.
+// every cluster's record with shard-local cluster indices, scratch[audit_layout(C).result() ...]
+// the shard's raft_audit_t.
 hipError_t launch_audit(const DevSim& S, uint32_t width, void* rec, unsigned long long* scratch,
                         hipStream_t st) {
   const bool wide = width == AUD_WIDE;
-  if (wide) aud_launch<AUD_WIDE>(S, static_cast<uint4*>(rec), scratch, st);
-  else aud_launch<AUD_NARROW>(S, static_cast<uint4*>(rec), scratch, st);
-  hipLaunchKernelGGL(audit_fold_kernel, dim3(1), dim3(AUD_FOLD_BLOCK), 0, st,
-                     (const unsigned long long*)scratch,
-                     aud_grid(S.C, wide ? AUD_WIDE : AUD_NARROW), scratch + audit_result_word(S.C));
-  return hipGetLastError();
+  uint4* const r = static_cast<uint4*>(rec);
+  return launch_summary<raft_audit_t>(
+      audit_layout(S.C), scratch, aud_grid(S.C, wide ? AUD_WIDE : AUD_NARROW), st,
+      [&](dim3 grid, unsigned long long* part) {
+        if (wide) aud_pass<AUD_WIDE>(S, r, grid, part, st);
+        else aud_pass<AUD_NARROW>(S, r, grid, part, st);
+      });
 }
 
-// The selection over the C records of rec: *audit_total_ptr receives the total, out (cap records;
-// may be null when cap is 0) the first min(total, cap) matches.
+// The selection over the C records of rec: *audit_layout(C).total_ptr(scratch) receives the total,
+// out (cap records; may be null when cap is 0) the first min(total, cap) matches.
 hipError_t launch_audit_select(uint32_t C, uint32_t any, uint32_t all, uint32_t none,
                                const void* rec, unsigned long long* scratch, void* out,
                                uint32_t cap, hipStream_t st) {
   const aud_select src = {static_cast<const uint4*>(rec), C, any, all, none,
                           static_cast<uint4*>(out)};
-  return launch_compact(src, aud_counts(scratch, C), cap, st);
+  return launch_compact(src, audit_layout(C).counts_ptr(scratch), cap, st);
 }
 
 }  // namespace rs

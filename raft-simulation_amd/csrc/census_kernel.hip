@@ -14,9 +14,7 @@
 // Census: a fixed grid of workgroups strides over the wave-sized groups of clusters. Counts are
 // popcounts of ballots kept in scalar registers, sums and extrema one accumulator per lane; at the
 // end every workgroup reduces to one raft_census_t in scratch and a second, one-workgroup kernel
-// folds those. Every field is an integer sum, minimum or maximum, the only synchronisation between
-// workgroups is the launch boundary and there is no atomic anywhere: the result depends on no
-// arrival or dispatch order.
+// folds those (summary.hpp: no atomics, the result depends on no arrival or dispatch order).
 //
 // Selection: the compaction of compact.hpp (count / scan / scatter over chunks of consecutive
 // clusters, the one the violation query runs over its records) over the source at the end of this
@@ -25,48 +23,16 @@
 // cluster's first lane stands for it in the ballot that ranks the matches; the record's
 // per-cluster extrema are taken by shuffles over the cluster's lanes, in waves that hold a match
 // only.
-#include "compact.hpp"
+#include "summary.hpp"
 
 namespace rs {
 
-constexpr uint32_t CEN_BLOCK = COMPACT_BLOCK;        // four waves, also for the census proper
-constexpr uint32_t CEN_WAVES = CEN_BLOCK / 64;
-constexpr uint32_t CEN_MAX_GRID = 1024;              // census workgroups (= partial records) at most
-constexpr uint32_t CEN_FOLD_BLOCK = 1024;            // the folding workgroup: 16 waves
-constexpr uint32_t CEN_ROUNDS = 16;                  // selection: wave-groups per wave and chunk
-constexpr uint32_t CEN_F = sizeof(raft_census_t) / 8;   // u64 fields of a census
-static_assert(sizeof(raft_census_t) % 8 == 0 && CEN_F <= 64, "a census is at most 64 u64 fields");
+constexpr uint32_t CEN_BLOCK = SUMMARY_BLOCK;        // four waves, also for the census proper
+constexpr uint32_t CEN_WAVES = SUMMARY_WAVES;
+constexpr uint32_t CEN_F = summary_F<raft_census_t>; // u64 fields of a census
 static_assert(sizeof(raft_cluster_state_t) == 32, "raft_cluster_state_t is eight words");
 
 #define CEN_IDX(field) ((uint32_t)(offsetof(raft_census_t, field) / 8))
-
-// How field f of two censuses combines: 0 sum, 1 minimum, 2 maximum.
-__host__ __device__ inline int cen_op(uint32_t f) {
-  if (f == CEN_IDX(term_min)) return 1;
-  if (f == CEN_IDX(term_max) || f == CEN_IDX(commit_max) || f == CEN_IDX(len_max) ||
-      f == CEN_IDX(hwm_max))
-    return 2;
-  return 0;
-}
-__host__ __device__ inline uint64_t cen_unit(uint32_t f) { return cen_op(f) == 1 ? ~0ull : 0ull; }
-__host__ __device__ inline uint64_t cen_fold(uint32_t f, uint64_t a, uint64_t b) {
-  const int op = cen_op(f);
-  return op == 0 ? a + b : op == 1 ? (a < b ? a : b) : (a > b ? a : b);
-}
-
-// The wave-sized groups of CPW = floor(64 / N) clusters a shard of C clusters has.
-__host__ __device__ inline uint32_t cen_groups(uint32_t C, uint32_t N) {
-  const uint32_t CPW = 64 / N;
-  return (C + CPW - 1) / CPW;
-}
-// Selection chunks: CEN_WAVES * CEN_ROUNDS groups each, consecutive clusters.
-__host__ __device__ inline uint32_t cen_chunk_clusters(uint32_t N) {
-  return CEN_WAVES * CEN_ROUNDS * (64 / N);
-}
-__host__ __device__ inline uint32_t cen_chunks(uint32_t C, uint32_t N) {
-  const uint32_t cc = cen_chunk_clusters(N);
-  return (C + cc - 1) / cc;
-}
 
 // A lane's node and its cluster's facts (the facts are the same on every lane of the cluster).
 struct CenLane {
@@ -148,26 +114,10 @@ __device__ __forceinline__ CenLane cen_load(const uint32_t* __restrict__ hot, ui
   return n;
 }
 
-__device__ __forceinline__ bool cen_match(uint32_t cls, uint32_t any, uint32_t all, uint32_t none) {
-  return (any == 0 || (cls & any) != 0) && (cls & all) == all && (cls & none) == 0;
-}
-
-// Wave reductions of a lane value (all 64 lanes active), uniform result.
-__device__ __forceinline__ uint64_t cen_wave_fold(uint32_t f, uint64_t x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d);
-    x = cen_fold(f, x, (uint64_t)hi << 32 | lo);
-  }
-  return x;
-}
-
 // The census of the groups this workgroup strides over: part[blockIdx.x] (CEN_F u64 fields).
 __global__ void __launch_bounds__(CEN_BLOCK)
 census_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_t C, uint32_t L,
               uint32_t quorum, unsigned long long* __restrict__ part) {
-  __shared__ unsigned long long rec[CEN_WAVES][CEN_F];
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t slot = lane / N, k = lane - slot * N;
   const uint32_t groups = cen_groups(C, N);
@@ -211,58 +161,16 @@ census_kernel(const uint32_t* __restrict__ hot, uint32_t HB, uint32_t N, uint32_
       hmax = max(hmax, hwm);
     }
   }
-  // the wave's record: every lane takes part in the reductions, lane 0 stores. A wave's counts
-  // stay below 2^32 (64 lanes, at most 2^18 groups per wave: C * N < 2^31 over 4,096 waves).
-  unsigned long long* r = rec[wv];
-#pragma unroll
-  for (uint32_t f = 0; f < NCNT; ++f) {
-    const uint32_t s = wave_sum(cnt[f]);
-    if (lane == 0) r[f] = s;
-  }
-  const uint64_t w_tmin = cen_wave_fold(CEN_IDX(term_min), tmin);
-  const uint64_t w_tmax = cen_wave_fold(CEN_IDX(term_max), tmax);
-  const uint64_t w_tsum = cen_wave_fold(CEN_IDX(term_sum), tsum);
-  const uint64_t w_cmax = cen_wave_fold(CEN_IDX(commit_max), cmax);
-  const uint64_t w_csum = cen_wave_fold(CEN_IDX(commit_sum), csum);
-  const uint64_t w_lmax = cen_wave_fold(CEN_IDX(len_max), lmax);
-  const uint64_t w_lsum = cen_wave_fold(CEN_IDX(len_sum), lsum);
-  const uint64_t w_rqs = cen_wave_fold(CEN_IDX(req_queued), rqs);
-  const uint64_t w_rss = cen_wave_fold(CEN_IDX(res_queued), rss);
-  const uint64_t w_hmax = cen_wave_fold(CEN_IDX(hwm_max), hmax);
-  const uint64_t w_hsum = cen_wave_fold(CEN_IDX(hwm_sum), hsum);
-  if (lane == 0) {
-    r[CEN_IDX(term_min)] = w_tmin; r[CEN_IDX(term_max)] = w_tmax; r[CEN_IDX(term_sum)] = w_tsum;
-    r[CEN_IDX(commit_max)] = w_cmax; r[CEN_IDX(commit_sum)] = w_csum;
-    r[CEN_IDX(len_max)] = w_lmax; r[CEN_IDX(len_sum)] = w_lsum;
-    r[CEN_IDX(req_queued)] = w_rqs; r[CEN_IDX(res_queued)] = w_rss;
-    r[CEN_IDX(hwm_max)] = w_hmax; r[CEN_IDX(hwm_sum)] = w_hsum;
-  }
-  __syncthreads();
-  if (threadIdx.x < CEN_F) {
-    const uint32_t f = threadIdx.x;
-    uint64_t x = rec[0][f];
-#pragma unroll
-    for (uint32_t w = 1; w < CEN_WAVES; ++w) x = cen_fold(f, x, rec[w][f]);
-    part[(size_t)blockIdx.x * CEN_F + f] = x;
-  }
-}
-
-// One workgroup: out[0 .. CEN_F) = the np partial records folded field by field.
-__global__ void __launch_bounds__(CEN_FOLD_BLOCK)
-census_fold_kernel(const unsigned long long* __restrict__ part, uint32_t np,
-                   unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long acc[CEN_FOLD_BLOCK / 64][64];
-  const uint32_t f = threadIdx.x & 63, row = threadIdx.x >> 6;
-  uint64_t x = cen_unit(f);
-  if (f < CEN_F)
-    for (uint32_t p = row; p < np; p += CEN_FOLD_BLOCK / 64)
-      x = cen_fold(f, x, part[(size_t)p * CEN_F + f]);
-  acc[row][f] = x;
-  __syncthreads();
-  if (threadIdx.x < CEN_F) {
-    for (uint32_t r = 1; r < CEN_FOLD_BLOCK / 64; ++r) x = cen_fold(f, x, acc[r][f]);
-    out[f] = x;
-  }
+  // the eleven fields after the counts, widened. A wave's counts stay below 2^32 (64 lanes, at
+  // most 2^18 groups per wave: C * N < 2^31 over 4,096 waves).
+  uint64_t x[CEN_F - NCNT];
+  x[CEN_IDX(term_min) - NCNT] = tmin; x[CEN_IDX(term_max) - NCNT] = tmax;
+  x[CEN_IDX(term_sum) - NCNT] = tsum;
+  x[CEN_IDX(commit_max) - NCNT] = cmax; x[CEN_IDX(commit_sum) - NCNT] = csum;
+  x[CEN_IDX(len_max) - NCNT] = lmax; x[CEN_IDX(len_sum) - NCNT] = lsum;
+  x[CEN_IDX(req_queued) - NCNT] = rqs; x[CEN_IDX(res_queued) - NCNT] = rss;
+  x[CEN_IDX(hwm_max) - NCNT] = hmax; x[CEN_IDX(hwm_sum) - NCNT] = hsum;
+  summary_block_store<raft_census_t, NCNT>(cnt, x, part);
 }
 
 // The selection's source for the compaction (compact.hpp): group (round * CEN_WAVES + wave) of the
@@ -290,7 +198,7 @@ struct cen_select {
     return it;
   }
   __device__ __forceinline__ bool match(const Item& it) const {
-    return it.n.head && cen_match(it.n.classes, any, all, none);
+    return it.n.head && class_match(it.n.classes, any, all, none);
   }
   // the record's extrema and sum over the cluster's N lanes, gathered by its first lane
   __device__ __forceinline__ void gather(Item& it) const {
@@ -315,58 +223,29 @@ struct cen_select {
   }
 };
 
-static uint32_t cen_grid(uint32_t C, uint32_t N) {
-  const uint32_t wg = (cen_groups(C, N) + CEN_WAVES - 1) / CEN_WAVES;
-  return wg < CEN_MAX_GRID ? wg : CEN_MAX_GRID;
-}
-
-// u64 words of the scratch array a shard's queries need: the census workgroups' partial records
-// and the folded census, then (as u32) the selection's compaction scratch.
-size_t census_scratch_words(uint32_t C, uint32_t N) {
-  return ((size_t)cen_grid(C, N) + 1) * CEN_F + (compact_scratch_words(cen_chunks(C, N)) + 1) / 2;
-}
-// Where the folded census / the selection's total stand in the scratch array.
-size_t census_result_word(uint32_t C, uint32_t N) { return (size_t)cen_grid(C, N) * CEN_F; }
-static uint32_t* cen_counts(unsigned long long* scratch, uint32_t C, uint32_t N) {
-  return reinterpret_cast<uint32_t*>(scratch + ((size_t)cen_grid(C, N) + 1) * CEN_F);
-}
-const uint32_t* census_total_ptr(unsigned long long* scratch, uint32_t C, uint32_t N) {
-  return compact_total_ptr(cen_counts(scratch, C, N), cen_chunks(C, N));
-}
-
 uint32_t census_quorum(uint32_t N, uint32_t variant) {
   return variant & RAFT_VARIANT_SPEC ? N / 2 + 1 : (N + 1) >> 1;
 }
 
-// acc <- acc folded with x, field by field (the host's reduction over shards).
-void census_init(raft_census_t* acc) {
-  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
-  for (uint32_t f = 0; f < CEN_F; ++f) a[f] = cen_unit(f);
-}
-void census_combine(raft_census_t* acc, const raft_census_t* x) {
-  uint64_t* a = reinterpret_cast<uint64_t*>(acc);
-  const uint64_t* b = reinterpret_cast<const uint64_t*>(x);
-  for (uint32_t f = 0; f < CEN_F; ++f) a[f] = cen_fold(f, a[f], b[f]);
-}
-
-// The census of shard S: scratch[census_result_word(C, N) ...] receives its raft_census_t.
+// The census of shard S: scratch[census_layout(C, N).result() ...] receives its raft_census_t.
 hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream_t st) {
-  const uint32_t grid = cen_grid(S.C, S.N);
-  hipLaunchKernelGGL(census_kernel, dim3(grid), dim3(CEN_BLOCK), 0, st, (const uint32_t*)S.hot,
-                     S.HB, S.N, S.C, S.L, census_quorum(S.N, S.variant), scratch);
-  hipLaunchKernelGGL(census_fold_kernel, dim3(1), dim3(CEN_FOLD_BLOCK), 0, st,
-                     (const unsigned long long*)scratch, grid, scratch + (size_t)grid * CEN_F);
-  return hipGetLastError();
+  return launch_summary<raft_census_t>(
+      census_layout(S.C, S.N), scratch, cen_grid(S.C, S.N), st,
+      [&](dim3 grid, unsigned long long* part) {
+        hipLaunchKernelGGL(census_kernel, grid, dim3(CEN_BLOCK), 0, st, (const uint32_t*)S.hot,
+                           S.HB, S.N, S.C, S.L, census_quorum(S.N, S.variant), part);
+      });
 }
 
-// The selection over shard S: *census_total_ptr receives the total, out (cap records; may be null
-// when cap is 0) the first min(total, cap) matches with shard-local cluster indices.
+// The selection over shard S: *census_layout(C, N).total_ptr(scratch) receives the total, out (cap
+// records; may be null when cap is 0) the first min(total, cap) matches with shard-local cluster
+// indices.
 hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
                                 unsigned long long* scratch, void* out, uint32_t cap,
                                 hipStream_t st) {
   const cen_select src = {S.hot, S.HB, S.N, S.C, S.L, census_quorum(S.N, S.variant),
                           any, all, none, static_cast<uint4*>(out)};
-  return launch_compact(src, cen_counts(scratch, S.C, S.N), cap, st);
+  return launch_compact(src, census_layout(S.C, S.N).counts_ptr(scratch), cap, st);
 }
 
 }  // namespace rs

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "summary_host.hpp"
 
 namespace rs {
 hipError_t launch_tick(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st, hipEvent_t ev0,
@@ -25,22 +26,12 @@ size_t viol_scratch_words(uint32_t C);
 const uint32_t* viol_total_ptr(const uint32_t* scratch, uint32_t C);
 hipError_t launch_viol_query(const DevSim& S, uint32_t kinds, uint64_t t_lo, uint64_t t_hi,
                              uint32_t* scratch, void* out, uint32_t cap, hipStream_t st);
-// census_kernel.hip
-size_t census_scratch_words(uint32_t C, uint32_t N);
-size_t census_result_word(uint32_t C, uint32_t N);
-const uint32_t* census_total_ptr(unsigned long long* scratch, uint32_t C, uint32_t N);
-void census_init(raft_census_t* acc);
-void census_combine(raft_census_t* acc, const raft_census_t* x);
+// census_kernel.hip (its scratch: summary_host.hpp, census_layout)
 hipError_t launch_census(const DevSim& S, unsigned long long* scratch, hipStream_t st);
 hipError_t launch_census_select(const DevSim& S, uint32_t any, uint32_t all, uint32_t none,
                                 unsigned long long* scratch, void* out, uint32_t cap,
                                 hipStream_t st);
-// audit_kernel.hip
-size_t audit_scratch_words(uint32_t C);
-size_t audit_result_word(uint32_t C);
-const uint32_t* audit_total_ptr(unsigned long long* scratch, uint32_t C);
-void audit_init(raft_audit_t* acc);
-void audit_combine(raft_audit_t* acc, const raft_audit_t* x);
+// audit_kernel.hip (its scratch: audit_layout)
 hipError_t launch_audit(const DevSim& S, uint32_t width, void* rec, unsigned long long* scratch,
                         hipStream_t st);
 hipError_t launch_audit_select(uint32_t C, uint32_t any, uint32_t all, uint32_t none,
@@ -1195,6 +1186,58 @@ static int64_t sharded_query(raft_sim_t* r, uint32_t cap, Rec* out, const char* 
   return rc ? rc : sum;
 }
 
+// The sharded summary path of raft_census_read and raft_audit_read: every shard leaves its folded
+// T (summary.hpp) in its scratch, the host folds them in shard order. Every started shard is
+// waited for, also after an error (its copy writes part[d]); the first error wins; a shard's time
+// is recorded only on success.
+//   name, prepare, ms   as sharded_query's
+//   enqueue   (Shard*) -> hipError_t: launch the query on the shard's stream
+//   result    (Shard*) -> const unsigned long long*: where the shard's folded T will stand
+//   failed    (Shard*): called after the wait for a shard when the call has failed by then
+template <class T, class Prepare, class Enqueue, class Result, class Failed>
+static int sharded_summary(raft_sim_t* r, T* out, const char* name, Prepare prepare,
+                           Enqueue enqueue, Result result, double Shard::*ms, Failed failed) {
+  const size_t G = r->sh.size();
+  std::vector<T> part(G);
+  char herr[64];
+  snprintf(herr, sizeof herr, "HIP error in %s: %%s", name);
+  int rc = 0;
+  auto step = [&](hipError_t e) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, herr, hipGetErrorString(e));
+    return !rc;
+  };
+  size_t started = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    if (!step(hipSetDevice(s->cfg.device)) || (rc = prepare(s))) break;
+    ++started;
+    step(hipEventRecord(s->qev0, s->stream)) && step(enqueue(s)) &&
+        step(hipEventRecord(s->qev1, s->stream)) &&
+        step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]), result(s), sizeof(T) / 8));
+  }
+  rs::summary_init(out);
+  for (size_t d = 0; d < started; ++d) {
+    Shard* s = r->sh[d];
+    float t = 0;
+    step(hipSetDevice(s->cfg.device));
+    step(hipStreamSynchronize(s->stream));
+    if (rc) failed(s);
+    if (rc || !step(hipEventElapsedTime(&t, s->qev0, s->qev1))) continue;
+    s->*ms = t;
+    rs::summary_combine(out, &part[d]);
+  }
+  return rc;
+}
+
+// The body of the raftsim_diag_*_ms exports: the maximum over shards of a query's device time.
+static int diag_ms(raft_sim_t* r, double* ms, double Shard::*field) {
+  if (!r || !ms) return fail(-EINVAL, "null argument");
+  double m = 0;
+  for (Shard* s : r->sh) m = std::max(m, s->*field);
+  *ms = m;
+  return 0;
+}
+
 // Violation records (include/raftsim.h, "no reference counterpart").
 int64_t raft_viol_read(raft_sim_t* r, uint32_t kinds_mask, uint64_t t_lo, uint64_t t_hi,
                        raft_violation_t* out, uint32_t cap) {
@@ -1230,11 +1273,7 @@ int raft_viol_clear(raft_sim_t* r) {
 // Diagnostic (not part of include/raftsim.h): device time of the last raft_viol_read's kernels
 // (HIP events around them on each shard's stream), the maximum over shards, in ms.
 extern "C" int raftsim_diag_viol_ms(raft_sim_t* r, double* ms) {
-  if (!r || !ms) return fail(-EINVAL, "null argument");
-  double m = 0;
-  for (Shard* s : r->sh) m = std::max(m, s->viol_ms);
-  *ms = m;
-  return 0;
+  return diag_ms(r, ms, &Shard::viol_ms);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1242,46 +1281,20 @@ extern "C" int raftsim_diag_viol_ms(raft_sim_t* r, double* ms) {
 // kernels over the hot blocks on every shard's stream at once, behind whatever the shard has
 // enqueued. They touch neither the state nor the host's bookkeeping of it (storm_until,
 // keys_written, the steady path choice), so a certificate stays and the next step runs as it would
-// have. The census is folded over the shards on the host; selections go through sharded_query.
+// have. The census goes through sharded_summary, selections through sharded_query.
 static int census_prepare(Shard* s) {
   if (s->cscratch) return 0;
-  return dalloc(s, &s->cscratch, rs::census_scratch_words(s->C, s->N));   // freed by sh_destroy
+  return dalloc(s, &s->cscratch, rs::census_layout(s->C, s->N).words());   // freed by sh_destroy
 }
 
 int raft_census_read(raft_sim_t* r, raft_census_t* out) {
   if (!r || !out) return fail(-EINVAL, "null argument");
   if (r->poisoned) return unusable();
-  const size_t G = r->sh.size();
-  std::vector<raft_census_t> part(G);
-  int rc = 0;
-  auto step = [&](hipError_t e) {
-    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_census_read: %s", hipGetErrorString(e));
-    return !rc;
-  };
-  size_t started = 0;
-  for (size_t d = 0; d < G && !rc; ++d) {
-    Shard* s = r->sh[d];
-    if (!step(hipSetDevice(s->cfg.device)) || (rc = census_prepare(s))) break;
-    ++started;
-    step(hipEventRecord(s->qev0, s->stream)) &&
-        step(rs::launch_census(s->d, s->cscratch, s->stream)) &&
-        step(hipEventRecord(s->qev1, s->stream)) &&
-        step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]),
-                 (const unsigned long long*)s->cscratch + rs::census_result_word(s->C, s->N),
-                 sizeof(raft_census_t) / 8));
-  }
-  rs::census_init(out);
-  // every started shard is waited for, also after an error: its copy writes part[d]
-  for (size_t d = 0; d < started; ++d) {
-    Shard* s = r->sh[d];
-    float ms = 0;
-    step(hipSetDevice(s->cfg.device));
-    step(hipStreamSynchronize(s->stream));
-    if (rc || !step(hipEventElapsedTime(&ms, s->qev0, s->qev1))) continue;
-    s->census_ms = ms;
-    rs::census_combine(out, &part[d]);
-  }
-  return rc;
+  return sharded_summary(
+      r, out, "raft_census_read", census_prepare,
+      [](Shard* s) { return rs::launch_census(s->d, s->cscratch, s->stream); },
+      [](Shard* s) { return s->cscratch + rs::census_layout(s->C, s->N).result(); },
+      &Shard::census_ms, [](Shard*) {});
 }
 
 int64_t raft_census_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, uint32_t none_mask,
@@ -1295,7 +1308,7 @@ int64_t raft_census_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, 
   return sharded_query(
       r, cap, out, "raft_census_select", census_prepare,
       [&](Shard* s, raft_cluster_state_t* dout, uint32_t dcap, const uint32_t** dtotal) {
-        *dtotal = rs::census_total_ptr(s->cscratch, s->C, s->N);
+        *dtotal = rs::census_layout(s->C, s->N).total_ptr(s->cscratch);
         return rs::launch_census_select(s->d, any_mask, all_mask, none_mask, s->cscratch, dout,
                                         dcap, s->stream);
       },
@@ -1306,11 +1319,7 @@ int64_t raft_census_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, 
 // raft_census_select's kernels (HIP events around them on each shard's stream), the maximum over
 // shards, in ms.
 extern "C" int raftsim_diag_census_ms(raft_sim_t* r, double* ms) {
-  if (!r || !ms) return fail(-EINVAL, "null argument");
-  double m = 0;
-  for (Shard* s : r->sh) m = std::max(m, s->census_ms);
-  *ms = m;
-  return 0;
+  return diag_ms(r, ms, &Shard::census_ms);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1324,7 +1333,7 @@ extern "C" int raftsim_diag_census_ms(raft_sim_t* r, double* ms) {
 static int audit_prepare(Shard* s) {
   if (s->ascratch) return 0;
   int rc = dalloc(s, &s->arec, s->C);
-  if (!rc) rc = dalloc(s, &s->ascratch, rs::audit_scratch_words(s->C));   // freed by sh_destroy
+  if (!rc) rc = dalloc(s, &s->ascratch, rs::audit_layout(s->C).words());   // freed by sh_destroy
   return rc;
 }
 // Enqueue the pass unless the shard's records are those of the state as it stands.
@@ -1342,37 +1351,10 @@ static hipError_t audit_refresh(Shard* s) {
 int raft_audit_read(raft_sim_t* r, raft_audit_t* out) {
   if (!r || !out) return fail(-EINVAL, "null argument");
   if (r->poisoned) return unusable();
-  const size_t G = r->sh.size();
-  std::vector<raft_audit_t> part(G);
-  int rc = 0;
-  auto step = [&](hipError_t e) {
-    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_audit_read: %s", hipGetErrorString(e));
-    return !rc;
-  };
-  size_t started = 0;
-  for (size_t d = 0; d < G && !rc; ++d) {
-    Shard* s = r->sh[d];
-    if (!step(hipSetDevice(s->cfg.device)) || (rc = audit_prepare(s))) break;
-    ++started;
-    step(hipEventRecord(s->qev0, s->stream)) && step(audit_refresh(s)) &&
-        step(hipEventRecord(s->qev1, s->stream)) &&
-        step(d2h(s, reinterpret_cast<unsigned long long*>(&part[d]),
-                 (const unsigned long long*)s->ascratch + rs::audit_result_word(s->C),
-                 sizeof(raft_audit_t) / 8));
-  }
-  rs::audit_init(out);
-  // every started shard is waited for, also after an error: its copy writes part[d]
-  for (size_t d = 0; d < started; ++d) {
-    Shard* s = r->sh[d];
-    float ms = 0;
-    step(hipSetDevice(s->cfg.device));
-    step(hipStreamSynchronize(s->stream));
-    if (rc) s->audit_valid = false;
-    if (rc || !step(hipEventElapsedTime(&ms, s->qev0, s->qev1))) continue;
-    s->audit_ms = ms;
-    rs::audit_combine(out, &part[d]);
-  }
-  return rc;
+  return sharded_summary(
+      r, out, "raft_audit_read", audit_prepare, audit_refresh,
+      [](Shard* s) { return s->ascratch + rs::audit_layout(s->C).result(); },
+      &Shard::audit_ms, [](Shard* s) { s->audit_valid = false; });
 }
 
 int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, uint32_t none_mask,
@@ -1386,7 +1368,7 @@ int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, u
   const int64_t n = sharded_query(
       r, cap, out, "raft_audit_select", audit_prepare,
       [&](Shard* s, raft_audit_record_t* dout, uint32_t dcap, const uint32_t** dtotal) {
-        *dtotal = rs::audit_total_ptr(s->ascratch, s->C);
+        *dtotal = rs::audit_layout(s->C).total_ptr(s->ascratch);
         const hipError_t e = audit_refresh(s);
         return e != hipSuccess ? e
                                : rs::launch_audit_select(s->C, any_mask, all_mask, none_mask,
@@ -1404,11 +1386,7 @@ int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, u
 // shards, in ms. A query that found the records valid ran no pass: its time is the copy's or the
 // compaction's alone.
 extern "C" int raftsim_diag_audit_ms(raft_sim_t* r, double* ms) {
-  if (!r || !ms) return fail(-EINVAL, "null argument");
-  double m = 0;
-  for (Shard* s : r->sh) m = std::max(m, s->audit_ms);
-  *ms = m;
-  return 0;
+  return diag_ms(r, ms, &Shard::audit_ms);
 }
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was

@@ -285,10 +285,35 @@ class GpuBackend(Backend):
         self._census = _abi.bind(self._lib, "raft_census_", sigs=_abi._CENSUS_SIGS)
         self._audit = _abi.bind(self._lib, "raft_audit_", sigs=_abi._AUDIT_SIGS)
 
-    def _viol_read(self, mask, t_lo, t_hi, cap):
-        buf = (_abi.Violation * max(1, cap))()
-        n = int(self._viol["read"](self._h, mask, t_lo, t_hi, buf if cap else None, cap))
-        return self._check(n), buf
+    # -- what the three device-side queries share ------------------------------------------------
+    @staticmethod
+    def _mask(names, table, noun):
+        mask = 0
+        for k in names:
+            if k not in table:
+                raise ValueError(f"unknown {noun} {k!r} (one of {list(table)})")
+            mask |= table[k]
+        return mask
+
+    def _selected(self, fn, rec_type, args, limit):
+        """(total, the records copied) of the selection entry point fn(handle, *args, out, cap).
+        limit None: every match, at the cost of a first call that only counts them; limit 0: one
+        call, the total alone."""
+        def read(cap):
+            buf = (rec_type * max(1, cap))()
+            return self._check(int(fn(self._h, *args, buf if cap else None, cap))), buf
+
+        cap = read(0)[0] if limit is None else int(limit)
+        total, buf = read(cap)
+        return total, buf[:min(total, cap)]
+
+    def _diag_ms(self, symbol):
+        f = getattr(self._lib, symbol)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        ms = C.c_double()
+        self._check(f(self._h, C.byref(ms)))
+        return ms.value
 
     def violations(self, kinds=("election", "log", "complete"), t_lo=0, t_hi=None, limit=None):
         """The clusters the checker counted a violation for: (total, records). A cluster matches
@@ -299,22 +324,14 @@ class GpuBackend(Backend):
         cluster), first_tick, election / log / complete (the cluster's counts) and kinds (the
         names of its nonzero counts). The selection runs on the device; only the records asked for
         are copied."""
-        mask = 0
-        for k in kinds:
-            if k not in _abi.VIOL_KINDS:
-                raise ValueError(f"unknown violation kind {k!r} (one of {list(_abi.VIOL_KINDS)})")
-            mask |= _abi.VIOL_KINDS[k]
+        mask = self._mask(kinds, _abi.VIOL_KINDS, "violation kind")
         t_hi = 2 ** 64 - 1 if t_hi is None else int(t_hi)
-        if limit is None:
-            total, _ = self._viol_read(mask, int(t_lo), t_hi, 0)
-            cap = total
-        else:
-            cap = int(limit)
-        total, buf = self._viol_read(mask, int(t_lo), t_hi, cap)
+        total, found = self._selected(self._viol["read"], _abi.Violation, (mask, int(t_lo), t_hi),
+                                      limit)
         off = self.config.cluster_offset
         names = list(_abi.VIOL_KINDS)
         recs = []
-        for v in buf[:min(total, cap)]:
+        for v in found:
             rec = {"cluster": v.cluster, "global_id": off + v.cluster, "first_tick": v.first_tick}
             rec.update(zip(names, v.count))
             rec["kinds"] = tuple(n for n in names if v.kinds & _abi.VIOL_KINDS[n])
@@ -327,12 +344,7 @@ class GpuBackend(Backend):
 
     def last_violations_ms(self):
         """Diagnostic: device time (HIP events) of the last violations() query's kernels."""
-        f = self._lib.raftsim_diag_viol_ms
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        ms = C.c_double()
-        self._check(f(self._h, C.byref(ms)))
-        return ms.value
+        return self._diag_ms("raftsim_diag_viol_ms")
 
     # -- state census (include/raftsim.h, "State census") ---------------------------------------
     def census(self):
@@ -350,18 +362,7 @@ class GpuBackend(Backend):
 
     @staticmethod
     def _class_mask(names):
-        mask = 0
-        for k in names:
-            if k not in _abi.CLUSTER_CLASSES:
-                raise ValueError(f"unknown cluster class {k!r} (one of "
-                                 f"{list(_abi.CLUSTER_CLASSES)})")
-            mask |= _abi.CLUSTER_CLASSES[k]
-        return mask
-
-    def _census_select(self, masks, cap):
-        buf = (_abi.ClusterState * max(1, cap))()
-        n = int(self._census["select"](self._h, *masks, buf if cap else None, cap))
-        return self._check(n), buf
+        return GpuBackend._mask(names, _abi.CLUSTER_CLASSES, "cluster class")
 
     def select(self, any=(), all=(), none=(), limit=None):
         """The clusters in given state classes: (total, records). A cluster matches when it is in
@@ -375,16 +376,11 @@ class GpuBackend(Backend):
         copied. On a run from init-node, raftsim.replay(sim, rec["cluster"]) reruns a selected
         cluster alone with its `wait` trace."""
         masks = [self._class_mask(x) for x in (any, all, none)]
-        if limit is None:
-            total, _ = self._census_select(masks, 0)
-            cap = total
-        else:
-            cap = int(limit)
-        total, buf = self._census_select(masks, cap)
+        total, found = self._selected(self._census["select"], _abi.ClusterState, masks, limit)
         off = self.config.cluster_offset
         ids = range(1, self.N + 1)
         recs = []
-        for v in buf[:min(total, cap)]:
+        for v in found:
             recs.append({
                 "cluster": v.cluster, "global_id": off + v.cluster,
                 "classes": tuple(k for k, b in _abi.CLUSTER_CLASSES.items() if v.classes & b),
@@ -396,12 +392,7 @@ class GpuBackend(Backend):
 
     def last_census_ms(self):
         """Diagnostic: device time (HIP events) of the last census() or select() query's kernels."""
-        f = self._lib.raftsim_diag_census_ms
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        ms = C.c_double()
-        self._check(f(self._h, C.byref(ms)))
-        return ms.value
+        return self._diag_ms("raftsim_diag_census_ms")
 
     # -- log audit (include/raftsim.h, "Log audit") ----------------------------------------------
     def audit(self):
@@ -423,17 +414,7 @@ class GpuBackend(Backend):
 
     @staticmethod
     def _audit_mask(names):
-        mask = 0
-        for k in names:
-            if k not in _abi.AUDIT_CLASSES:
-                raise ValueError(f"unknown audit class {k!r} (one of {list(_abi.AUDIT_CLASSES)})")
-            mask |= _abi.AUDIT_CLASSES[k]
-        return mask
-
-    def _audit_select(self, masks, cap):
-        buf = (_abi.AuditRecord * max(1, cap))()
-        n = int(self._audit["select"](self._h, *masks, buf if cap else None, cap))
-        return self._check(n), buf
+        return GpuBackend._mask(names, _abi.AUDIT_CLASSES, "audit class")
 
     def audit_select(self, any=(), all=(), none=(), limit=None):
         """The clusters in given audit classes: (total, records), with the predicate and the
@@ -446,24 +427,14 @@ class GpuBackend(Backend):
         len_min (the shortest log). The selection runs on the device; only the records asked for
         are copied."""
         masks = [self._audit_mask(x) for x in (any, all, none)]
-        if limit is None:
-            total, _ = self._audit_select(masks, 0)
-            cap = total
-        else:
-            cap = int(limit)
-        total, buf = self._audit_select(masks, cap)
+        total, found = self._selected(self._audit["select"], _abi.AuditRecord, masks, limit)
         off = self.config.cluster_offset
-        return total, [v.as_dict(self.N, off) for v in buf[:min(total, cap)]]
+        return total, [v.as_dict(self.N, off) for v in found]
 
     def last_audit_ms(self):
         """Diagnostic: device time (HIP events) of the last audit() or audit_select() query's
         kernels."""
-        f = self._lib.raftsim_diag_audit_ms
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        ms = C.c_double()
-        self._check(f(self._h, C.byref(ms)))
-        return ms.value
+        return self._diag_ms("raftsim_diag_audit_ms")
 
     def replay_config(self, cluster, **overrides):
         """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster

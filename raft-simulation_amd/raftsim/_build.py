@@ -21,6 +21,8 @@ KERNEL_SOURCES = ["raft-simulation_amd/csrc/tick_kernel.hip",
                   "raft-simulation_amd/csrc/audit_kernel.hip",
                   "raft-simulation_amd/csrc/tick_wave.hpp", "raft-simulation_amd/csrc/device.hpp",
                   "raft-simulation_amd/csrc/compact.hpp",
+                  "raft-simulation_amd/csrc/summary.hpp",
+                  "raft-simulation_amd/csrc/summary_host.hpp",
                   "raft-simulation_amd/csrc/fixed_point_affine.hpp",
                   "raft-simulation_amd/csrc/raftsim.hip", "include/raftsim.h"]
 # "diag": a diagnostic build (csrc/device.hpp's switches, RS_DIAG_BUILD), whatever its sources

@@ -41,62 +41,51 @@ def reduce_counters(c: dict, device=None) -> dict:
     return out
 
 
+def _reduce_summary(s: dict, device=None) -> dict:
+    """All-reduce a census or audit dict over the default process group, three collectives: MAX of
+    the *_max fields, MIN of the *_min fields (None: the rank has none, NONE_TICK on the wire), SUM
+    of everything else; dict- and list-valued fields (by_class, the histograms) element by
+    element. The output keeps the input's key order."""
+    import torch
+    import torch.distributed as dist
+
+    def op(k):
+        return "MAX" if k.endswith("_max") else "MIN" if k.endswith("_min") else "SUM"
+
+    flat = {"SUM": [], "MAX": [], "MIN": []}
+    for k, v in s.items():
+        vals = v.values() if isinstance(v, dict) else v if isinstance(v, list) else [v]
+        flat[op(k)] += [NONE_TICK if x is None else int(x) for x in vals]
+    red = {}
+    for name, vals in flat.items():
+        t = torch.tensor(vals, dtype=torch.int64, device=device)
+        dist.all_reduce(t, op=getattr(dist.ReduceOp, name))
+        red[name] = iter(int(x) for x in t.tolist())
+    out = {}
+    for k, v in s.items():
+        it = red[op(k)]
+        if isinstance(v, dict):
+            out[k] = {c: next(it) for c in v}
+        elif isinstance(v, list):
+            out[k] = [next(it) for _ in v]
+        else:
+            x = next(it)
+            out[k] = None if op(k) == "MIN" and x == NONE_TICK else x
+    return out
+
+
 def reduce_census(c: dict, device=None) -> dict:
     """All-reduce a census dict (Simulator.census()) over the default process group: SUM of the
     counts and sums (the histograms and per-class counts element by element), MIN of term_min, MAX
     of the *_max fields. Every rank must hold a census of the same `nodes` per cluster."""
-    import torch
-    import torch.distributed as dist
-
-    maxes = sorted(k for k in c if k.endswith("_max"))
-    lists = sorted(k for k, v in c.items() if isinstance(v, list))
-    classes = list(c["by_class"])
-    sums = sorted(k for k, v in c.items()
-                  if k not in maxes and k != "term_min" and not isinstance(v, (list, dict)))
-    flat = [int(c[k]) for k in sums] + [int(c["by_class"][k]) for k in classes]
-    for k in lists:
-        flat += [int(x) for x in c[k]]
-    v = torch.tensor(flat, dtype=torch.int64, device=device)
-    dist.all_reduce(v, op=dist.ReduceOp.SUM)
-    mx = torch.tensor([int(c[k]) for k in maxes], dtype=torch.int64, device=device)
-    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-    mn = torch.tensor([int(c["term_min"])], dtype=torch.int64, device=device)
-    dist.all_reduce(mn, op=dist.ReduceOp.MIN)
-    it = iter(int(x) for x in v.tolist())
-    out = {k: next(it) for k in sums}
-    out["by_class"] = {k: next(it) for k in classes}
-    for k in lists:
-        out[k] = [next(it) for _ in c[k]]
-    out.update(zip(maxes, (int(x) for x in mx.tolist())))
-    out["term_min"] = int(mn.item())
-    return {k: out[k] for k in c}
+    return _reduce_summary(c, device)
 
 
 def reduce_audit(a: dict, device=None) -> dict:
     """All-reduce an audit dict (Simulator.audit()) over the default process group: SUM of the
     counts and sums (the per-class counts element by element), MIN of agree_min and the
     *_index_min fields (None: no cluster of the rank has one), MAX of agree_max."""
-    import torch
-    import torch.distributed as dist
-
-    mins = sorted(k for k in a if k.endswith("_min"))
-    maxes = sorted(k for k in a if k.endswith("_max"))
-    classes = list(a["by_class"])
-    sums = sorted(k for k in a if k not in mins and k not in maxes and k != "by_class")
-    v = torch.tensor([int(a[k]) for k in sums] + [int(a["by_class"][k]) for k in classes],
-                     dtype=torch.int64, device=device)
-    dist.all_reduce(v, op=dist.ReduceOp.SUM)
-    mx = torch.tensor([int(a[k]) for k in maxes], dtype=torch.int64, device=device)
-    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-    mn = torch.tensor([NONE_TICK if a[k] is None else int(a[k]) for k in mins],
-                      dtype=torch.int64, device=device)
-    dist.all_reduce(mn, op=dist.ReduceOp.MIN)
-    it = iter(int(x) for x in v.tolist())
-    out = {k: next(it) for k in sums}
-    out["by_class"] = {k: next(it) for k in classes}
-    out.update(zip(maxes, (int(x) for x in mx.tolist())))
-    out.update((k, None if x == NONE_TICK else x) for k, x in zip(mins, (int(x) for x in mn.tolist())))
-    return {k: out[k] for k in a}
+    return _reduce_summary(a, device)
 
 
 def reduce_max(x: float, device=None) -> float:

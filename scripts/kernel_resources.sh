@@ -41,6 +41,9 @@ for m in re.finditer(r'^(_ZN2rs\w+):\s', s, re.M):
     mc = re.match(r'rs::\d+((?:census|viol|audit)_\w*?kernel)E', pretty)
     if mc:
         pretty = mc.group(1)
+    mf = re.match(r'rs::19summary_fold_kernelI\d+raft_([a-z]+)E', pretty)
+    if mf:
+        pretty = f"summary_fold_kernel<{mf.group(1)}>"
     ma = re.match(r'rs::12audit_kernelILj(\d)ELj(\d+)E', pretty)
     if ma:
         pretty = f"audit_kernel<N={ma.group(1)}, G={ma.group(2)}>"

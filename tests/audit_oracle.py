@@ -8,6 +8,8 @@ suite); run on a GPU handle's own read-back it checks host-written logs no run r
 """
 from __future__ import annotations
 
+from class_predicate import matches
+
 CLASSES = {"diverged": 1, "commit_diverged": 2, "match_broken": 4, "term_order": 8,
            "identical": 16}
 SCALARS = ("entries", "agree_sum", "agree_min", "agree_max", "diverged_nodes",
@@ -78,12 +80,6 @@ def summary_of(recs, logs):
             "commit_diverged_nodes": sum(len(r["commit_diverged"]) for r in recs),
             "diverge_index_min": min(div) if div else None,
             "commit_diverge_index_min": min(cdiv) if cdiv else None}
-
-
-def matches(rec, any=(), all=(), none=()):
-    """The selection predicate of raft_audit_select on a record's class names."""
-    have = set(rec["classes"])
-    return ((not any or bool(have & set(any))) and set(all) <= have and not (have & set(none)))
 
 
 def select_of(recs, any=(), all=(), none=(), limit=None):

@@ -7,6 +7,8 @@ the GPU's (the parity suite), so the census of the oracle's records is the censu
 """
 from __future__ import annotations
 
+from class_predicate import matches
+
 MAX_NODES = 9
 CLASSES = {"no_leader": 1, "one_leader": 2, "multi_leader": 4, "halted": 8, "no_quorum": 16,
            "same_term_leaders": 32, "log_full": 64, "candidate": 128, "settled": 256}
@@ -86,12 +88,6 @@ def census_of(nodes, clusters, n_nodes, log_cap, variant_flags):
                len_sum=sum(lens), req_queued=sum(r["req_count"] for r in nodes),
                res_queued=sum(r["res_count"] for r in nodes), hwm_max=max(hwm), hwm_sum=sum(hwm))
     return out
-
-
-def matches(rec, any=(), all=(), none=()):
-    """The selection predicate of raft_census_select on a record's class names."""
-    have = set(rec["classes"])
-    return ((not any or bool(have & set(any))) and set(all) <= have and not (have & set(none)))
 
 
 def select_of(recs, any=(), all=(), none=(), limit=None):

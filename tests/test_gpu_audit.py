@@ -63,10 +63,11 @@ def test_audit_and_selection_equal_the_mirror_on_the_oracle(name, n, ticks):
 
 # -- host-written logs -----------------------------------------------------------------------------
 
-def write_shapes(g, shapes, A):
-    """One cluster per shape: the arenas (poison outside the logs), then the node records."""
+def write_shapes(g, shapes, A, where=None):
+    """One cluster per shape (shape i at cluster where[i], or i): the arenas (poison outside the
+    logs), then the node records."""
     N = g.N
-    for c, sh in enumerate(shapes):
+    for c, sh in zip(where or range(len(shapes)), shapes):
         bases = audit_shapes.bases(N, A, c, sh)
         raw = list(g.read_nodes_raw(c, 1))
         for k, node in enumerate(raw):
@@ -154,6 +155,86 @@ def test_records_stay_valid_until_a_log_or_commit_changes():
     assert g.audit() == s0 and g.audit_select() == (333, r0)
     g.step(1000)
     assert g.audit_select() == (333, r1) and g.audit() == s1
+    g.close()
+
+
+# -- the capped grid -------------------------------------------------------------------------------
+
+def capped_handle(width, C):
+    """A handle past the pass's grid cap at `width` lanes per cluster (2,048 workgroups of four
+    waves: 8,192 groups of 64 / width clusters a trip), N = 3, fresh from init-node, with four
+    written clusters: at cluster 0, at the last cluster of the first trip, at the first of the
+    second and at C - 1. Returns (handle, their clusters, the expected audit(), the expected
+    records of the written clusters): the mirror on the read-back of the written clusters and of
+    one untouched cluster, that one scaled by the number of untouched clusters."""
+    N, log_cap, A = 3, 24, 51
+    trip = 2048 * 4 * (64 // width)
+    assert trip < C < 2 * trip
+    where = [0, trip - 1, trip, C - 1]
+    by_name = {s["name"]: s for s in audit_shapes.shapes(N, log_cap)}
+    shapes = [by_name[k] for k in ("diff_term_0", "order_one_15", "match_step16", "identical_17")]
+    assert "commit_diverged" in shapes[0]["want"] and "term_order" in shapes[1]["want"]
+    assert shapes[2]["want"] == ("diverged", "match_broken") and shapes[3]["want"] == ("identical",)
+    g = helpers.gpu(n_clusters=C, nodes=N, log_cap=log_cap, arena_cap=A, seed=3)
+    write_shapes(g, shapes, A, where)
+
+    def one(c):
+        nodes = g.read_nodes(c, 1)
+        logs = [g.log(c, k + 1) if r["log_len"] else [] for k, r in enumerate(nodes)]
+        rec = ao.records_of(logs, [r["commit_index"] for r in nodes], N)[0]
+        rec = dict(rec, cluster=c, global_id=c)
+        return ao.summary_of([rec], logs), rec
+    (init, irec), wrote = one(1), [one(c) for c in where]
+    assert irec["classes"] == ("identical",) and init["entries"] == 0
+    for (_, rec), sh in zip(wrote, shapes):
+        assert rec["classes"] == tuple(k for k in ao.CLASSES if k in sh["want"]), sh["name"]
+    a, parts = C - len(where), [s for s, _ in wrote]
+    want = {}
+    for k, v in init.items():
+        ws = [s[k] for s in parts]
+        if k == "by_class":
+            want[k] = {x: a * v[x] + sum(w[x] for w in ws) for x in v}
+        elif k.endswith("_min") or k.endswith("_max"):
+            have = [x for x in [v] + ws if x is not None]
+            want[k] = (min if k.endswith("_min") else max)(have) if have else None
+        else:
+            want[k] = a * v + sum(ws)
+    assert want["clusters"] == C and want["by_class"]["identical"] == a + 1
+    assert want["agree_min"] == 0 and want["agree_max"] == 17 and want["diverge_index_min"] == 0
+    return g, where, want, [rec for _, rec in wrote]
+
+
+@pytest.mark.parametrize("width,C", [(64, 8197), (16, 32789)])
+def test_capped_grid_strides_to_a_second_trip(width, C, monkeypatch):
+    """The smallest shapes at which the pass's grid is capped. Width 64: 8,197 groups over 8,192
+    waves, so groups 8,192 .. 8,196 are a second trip, spread over two workgroups. Width 16: 8,198
+    groups of four clusters, the last holding one cluster. Either way the fold kernel sees 2,048
+    partial summaries. Written clusters stand on both sides of the trip's edge and at both ends."""
+    monkeypatch.setenv("RAFTSIM_AUDIT_WIDTH", str(width))
+    g, where, want, recs = capped_handle(width, C)
+    got = g.audit()
+    assert got == want and list(got) == list(want)
+    check_identities(got)
+    assert g.audit_select(none=("identical",)) == (3, recs[:3])
+    assert [r["cluster"] for r in recs[:3]] == where[:3]
+    assert g.audit_select(limit=0) == (C, [])
+    assert g.audit_select(any=("identical",), limit=0) == (C - 3, [])
+    g.close()
+
+
+def test_one_handle_serves_both_widths(monkeypatch):
+    """The scratch a handle allocates at its first query serves either width: on the 8,197-cluster
+    handle a query at width 16, then (a node record written back unchanged makes the next query
+    walk the logs again) at 64, at 64 again and at 16 give the same answers. The wide grid there
+    is 2,048 workgroups, the narrow one 513."""
+    monkeypatch.setenv("RAFTSIM_AUDIT_WIDTH", "16")
+    g, _, want, recs = capped_handle(64, 8197)
+    answers = []
+    for width in (16, 64, 64, 16):
+        monkeypatch.setenv("RAFTSIM_AUDIT_WIDTH", str(width))
+        g.write_nodes(0, list(g.read_nodes_raw(0, 1)))
+        answers.append((g.audit(), g.audit_select(none=("identical",))))
+    assert answers == [(want, (3, recs[:3]))] * 4
     g.close()
 
 
