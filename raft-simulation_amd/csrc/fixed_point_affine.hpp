@@ -135,6 +135,40 @@ FPA_FN Set compose(const Set& f, const Set& g, uint32_t P) {
 
 FPA_FN uint32_t period(int F, uint32_t d, uint32_t hb) { return 2 * d + (uint32_t)F - 1 + hb; }
 
+// The band of a launch of nt ticks from t0. A cluster on the schedule has its first heartbeat of
+// the launch at th = t0 + delta with 0 <= delta < P, and runs
+//   K(delta) = tend > th + last ? (tend - th - last - 1) / P + 1 : 0      (last = 2d + F - 1)
+// whole rounds before tend = t0 + nt. With R = nt - last - 1 = (K1 - 1) P + rho, 0 <= rho < P:
+// delta <= rho leaves (R - delta) / P = K1 - 1, so K = K1; rho < delta < P leaves
+// R - delta = (K1 - 2) P + (P + rho - delta) with 0 < P + rho - delta < P, so K = K1 - 1 (at
+// K1 = 1: R = rho < delta, tend <= th + last, K = 0). Hence K(delta) = K1 - (delta > rho): one
+// comparison per cluster against launch constants, no division. nt <= last: K = K1 = 0 for every
+// delta, and rho is a value no delta exceeds. The K rounds end at tk = th + K P, with
+// K1P = K1 * P and K1P - P both launch constants.
+struct Band {
+  uint32_t K1, rho, K1P;
+};
+FPA_FN Band band(int F, uint32_t d, uint32_t hb, uint32_t nt) {
+  const uint32_t P = period(F, d, hb), last = 2 * d + (uint32_t)F - 1;
+  Band b;
+  if (nt > last) {
+    const uint32_t R = nt - last - 1, q = R / P;
+    b.K1 = q + 1;
+    b.rho = R - q * P;
+    b.K1P = b.K1 * P;
+  } else {
+    b.K1 = 0;
+    b.rho = 0xFFFFFFFFu;
+    b.K1P = 0;
+  }
+  return b;
+}
+// The whole rounds of the cluster at delta, and the ticks they take.
+FPA_FN uint32_t band_rounds(const Band& b, uint32_t delta) { return b.K1 - (uint32_t)(delta > b.rho); }
+FPA_FN uint32_t band_ticks(const Band& b, uint32_t P, uint32_t delta) {
+  return b.K1P - (delta > b.rho ? P : 0u);
+}
+
 // K's set from (K - 1)'s.
 template <int F>
 FPA_FN Set step(const Set& c, uint32_t d, uint32_t hb) {

@@ -130,15 +130,25 @@ __device__ __forceinline__ SetWords vreg(const fpa::Set& c, uint32_t K1) {
                   vreg(c.fol.a),  vreg(c.fol.x),  vreg(c.fol.y),  vreg(c.fol.z),
                   vreg(c.lead.s), vreg(c.fol.s),  vreg(c.K),      vreg(K1)};
 }
+// Lane I of `park` takes the wave-uniform v: v_writelane, kept in program order with the other asm
+// statements (the loads' issue before it, their wait behind it).
+template <int I>
+__device__ __forceinline__ void park_lane(uint32_t& park, uint32_t v) {
+  asm volatile("v_writelane_b32 %0, %1, %2"
+               : "+v"(park)
+               : "s"(__builtin_amdgcn_readfirstlane(v)), "n"(I));
+}
 // The sets of a launch of nt ticks into *out. Uniform arguments: scalar code, moved to vector
 // registers (the stores' data) by instructions the compiler keeps in program order.
+// Returns the launch's band (K1, rho, K1 * P), from the same division.
 template <int F>
-__device__ __forceinline__ void band_sets(uint32_t nt, uint32_t d, uint32_t hb, BandSets* out) {
-  const uint32_t P = fpa::period(F, d, hb), last = 2 * d + F - 1;
-  const uint32_t K1 = nt > last ? (nt - last - 1) / P + 1 : 0;
+__device__ __forceinline__ fpa::Band band_sets(uint32_t nt, uint32_t d, uint32_t hb, BandSets* out) {
+  const fpa::Band b = fpa::band(F, d, hb, nt);
+  const uint32_t K1 = b.K1;
   const fpa::Set lo = fpa::build<F>(d, hb, K1 ? K1 - 1 : 0), hi = fpa::step<F>(lo, d, hb);
   out->k[0] = vreg(lo, K1);
   out->k[1] = vreg(hi, K1);
+  return b;
 }
 
 // A cluster at its fixed point, lane-resident: every follower took the leader's append-entries
@@ -151,6 +161,7 @@ __device__ __forceinline__ void band_sets(uint32_t nt, uint32_t d, uint32_t hb, 
 template <int N>
 struct FixedPoint {
   static constexpr int F = N - 1;
+  static constexpr bool IN_BAND = false;             // rounds(): any K
   uint32_t L, Lid, Lterm, Lcommit;
   uint64_t Ltr, ftr[F];
   uint32_t Ldl, fdl[F], fpend;                       // fpend: followers whose draw is owed
@@ -276,6 +287,7 @@ struct FixedPoint {
 template <int N>
 struct NodeOrder {
   static constexpr int F = N - 1;
+  static constexpr bool IN_BAND = true;              // rounds(): th is in [t0, t0 + P), tested
   uint32_t L, T;                                     // the leader's index; every node's term
   uint64_t tr[N], Ltr;                               // hashes by node (tr[L] dead); the leader's
   uint32_t Ldl;
@@ -328,14 +340,42 @@ struct NodeOrder {
 // the two counts the wave's sets hold, as it is for every cluster on the schedule; when some lane
 // here has another K (set_tick moved the clock, an election ended mid-launch, ...) all of them
 // take the loop over rounds instead.
+//
+// The band form (St::IN_BAND: the line-0 body, whose decision tested th - t0 < P): K is K1 or
+// K1 - 1 by one comparison against the launch's band (fixed_point_affine.hpp, Band), the set is
+// picked by it, and the set of no round is the identity, so the step is taken by every lane: no
+// division, no read of K1, no ballot and no loop.
+struct LaunchBand {
+  uint32_t t0;
+  fpa::Band b;
+};
 template <typename St>
 __device__ __forceinline__ void rounds(St& s, uint32_t th, uint32_t tend, uint32_t d, uint32_t hb,
-                                       uint32_t el_base, const BandSets& bs) {
+                                       uint32_t el_base, const BandSets& bs, const LaunchBand& lb) {
   constexpr int F = St::F;
   const uint32_t P = 2 * d + F - 1 + hb, last = 2 * d + F - 1, T = s.term();
-  const uint32_t K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
-  const uint32_t tk = th + K * P;
-  if (K) {
+  uint32_t K, tk;
+  if constexpr (St::IN_BAND) {
+    const uint32_t delta = th - lb.t0;
+    K = fpa::band_rounds(lb.b, delta);
+    tk = th + fpa::band_ticks(lb.b, P, delta);
+    // k[1] holds K1 rounds and k[0] K1 - 1; at K1 = 0 both K's set is k[0], the identity
+    const SetWords sw = bs.k[(delta <= lb.b.rho) & (lb.b.K1 != 0)];
+    const fpa::Half cl = sw.lead(), cf = sw.fol();
+    s.Ltr = fpa::apply_leader<F>(cl, s.Ltr, th, T, s.L);
+    s.followers(cf.a, fpa::follower_addend<F>(cf, th, T, s.L));
+    if (K) {
+      s.rearmed(tk - P + d + el_base);
+      s.Ldl = tk;
+      s.nhb += K;
+      s.nae += F * K;
+      s.nar += F * K;
+    }
+  } else {
+    K = tend > th + last ? (tend - th - last - 1) / P + 1 : 0;
+    tk = th + K * P;
+  }
+  if (!St::IN_BAND && K) {
     const uint32_t K1 = bs.k[0].K1;
     const bool top = K == K1;
     if (!__builtin_amdgcn_ballot_w64(!top && K + 1 != K1)) {   // uniform over the lanes here
@@ -387,7 +427,7 @@ __device__ __forceinline__ void rounds(St& s, uint32_t th, uint32_t tend, uint32
 template <typename St>
 __device__ __forceinline__ void run_launch(St& s, uint32_t mid, uint32_t th0, uint32_t tend,
                                            uint32_t d, uint32_t hb, uint32_t el_base, uint32_t P,
-                                           const BandSets& bs) {
+                                           const BandSets& bs, const LaunchBand& lb) {
   bool whole = true;                              // the round in progress finished in this launch
   if (mid == 1) {
     if (th0 + d < tend) s.append_entries(th0 + d, d, el_base);
@@ -397,7 +437,7 @@ __device__ __forceinline__ void run_launch(St& s, uint32_t mid, uint32_t th0, ui
     s.responses(th0, tend, d, hb);
     whole = !s.queued();
   }
-  if (whole) rounds(s, mid ? th0 + P : th0, tend, d, hb, el_base, bs);
+  if (whole) rounds(s, mid ? th0 + P : th0, tend, d, hb, el_base, bs, lb);
 }
 
 // Which round of the period-P schedule is in progress at t0, from the leader's deadline Ldl and
@@ -562,16 +602,32 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   uint32_t nt_s = nt;
   asm volatile("" : "+s"(nt_s));
   const BandSets& bs = bs_keep[wave];
-  band_sets<F>(nt_s, S.dmin, S.hb, &bs_keep[wave]);
+  // The launch's band (K1, rho, K1 * P: scalar values of the same build) waits for the rounds in
+  // three lanes of one vector register, written here in the load's shadow and read back on the
+  // scalar unit behind the wait (v_writelane / v_readlane, as the compiler's own scalar spills):
+  // no LDS round trip, no scalar register held across the decision.
+  uint32_t park = 0;
+  {
+    const fpa::Band b = band_sets<F>(nt_s, S.dmin, S.hb, &bs_keep[wave]);
+    park_lane<0>(park, b.K1);
+    park_lane<1>(park, b.rho);
+    park_lane<2>(park, b.K1P);
+  }
   load_wait();
+  asm volatile("" : "+v"(park));               // (no read of it moves above the wait)
+  auto parked_band = [&]() {
+    return fpa::Band{(uint32_t)__builtin_amdgcn_readlane(park, 0),
+                     (uint32_t)__builtin_amdgcn_readlane(park, 1),
+                     (uint32_t)__builtin_amdgcn_readlane(park, 2)};
+  };
   if (reporter && prev_bails) {
     if (S.bail_report) *S.bail_report = prev_bails;
     *S.nbail_zero = 0;
   }
   static_assert(NW4 >= 8, "line 0 is read whole");
   read_chunks(0, 8);
-  const uint32_t tend = t0 + nt, d = S.dmin;
-  const uint32_t P = 2 * d + F - 1 + S.hb, allF = (1u << F) - 1;
+  const uint32_t tend = t0 + nt, d = S.dmin, hb = S.hb, el_base = S.el_base;
+  const uint32_t P = 2 * d + F - 1 + hb, allF = (1u << F) - 1;
   uint32_t dl = 0, nhb = 0, nae = 0, nar = 0;  // lines of the block changed; events run
   bool el = false;                             // the cluster's election ran here (general path)
   uint32_t el_to = 0;                          // its timeouts (two candidates: a tie)
@@ -599,9 +655,11 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   // slots. A follower is "a node that is not L".
   NodeOrder<N> no;
   uint32_t lmid = 0, lth0 = 0;
-  const bool cfg_ok = S.el_base >= P && S.hb >= 2 * d + F && S.Q >= (uint32_t)F;
-  bool strong = active && cfg_ok && (w[CL_CERT] & 0xFFFF0000u) == CERT_STRONG &&
-                (w[CL_CERT] & 0xFFFFu) < (uint32_t)N;
+  const bool cfg_ok = el_base >= P && hb >= 2 * d + F && S.Q >= (uint32_t)F;
+  // (The tests are combined with & on values already in registers and the three cases of the
+  // round in progress are selects: no branch in the decision.)
+  bool strong = active & cfg_ok & ((w[CL_CERT] & 0xFFFF0000u) == CERT_STRONG) &
+                ((w[CL_CERT] & 0xFFFFu) < (uint32_t)N);
   {
     const uint32_t L = w[CL_CERT] & 0xFFFFu;
     no.L = L; no.T = w[CL_CTERM];
@@ -609,47 +667,47 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     no.Ltr = (uint64_t)lword(HF_TRACE_HI, L) << 32 | lword(HF_TRACE_LO, L);
 #pragma unroll
     for (int k = 0; k < N; ++k) no.tr[k] = (uint64_t)word(HF_TRACE_HI, k) << 32 | word(HF_TRACE_LO, k);
-    no.qin = no.took = false; no.qA = no.fdl = 0; no.rc = 0; no.resA = INF;
+    no.took = false; no.fdl = 0;
     no.nhb = no.nae = no.nar = 0;
     const uint32_t Lqm = lword(HF_QMETA, L), rsc = qm_res_cnt(Lqm);
     // a certified block's rings have their heads at slot 0: the followers' QMETA words are all
     // "no message" or all "one request", the leader's is its response count
     const uint32_t qm0 = L ? word(HF_QMETA, 0) : word(HF_QMETA, 1);   // the first follower's
-    const bool need = qm0 != 0;
-    strong = strong && (qm0 & ~pack_qmeta(0, 1, 0, 0)) == 0 && Lqm == pack_qmeta(0, 0, 0, rsc) &&
-             rsc <= (uint32_t)F && !(need && rsc);
+    const bool need = qm0 != 0;                     // the append-entries in flight
+    const bool cutr = !need & (rsc != 0);           // the responses the last launch's end cut
+    const uint32_t one_req = pack_qmeta(0, 1, 0, 0), only_res = pack_qmeta(0, 0, 0, rsc);
+    strong = strong & ((qm0 & ~one_req) == 0) & (Lqm == only_res) & (rsc <= (uint32_t)F) &
+             !(need & (rsc != 0));
 #pragma unroll
-    for (int k = 0; k < N; ++k) strong = strong && (L == (uint32_t)k || word(HF_QMETA, k) == qm0);
-    lth0 = no.Ldl;
-    if (need) {                                     // the append-entries in flight
-      lmid = 1;
-      lth0 = no.Ldl - S.hb;
-      const uint32_t ta = lth0 + d;
-      strong = strong && no.Ldl >= S.hb && ta >= t0;
-      no.qin = true;
-      no.qA = ta;
-    } else if (rsc) {                               // the responses the last launch's end cut
-      lmid = 2;
-      // the leader's deadline is the round's heartbeat + hb until it takes a response, then that
-      // response's tick (th + 2d + j0 - 1 for the j0-th) + hb
-      const uint32_t j0 = (uint32_t)F - rsc, back = S.hb + (j0 ? 2 * d + j0 - 1 : 0u);
-      lth0 = no.Ldl - back;
-      const uint32_t ra = lth0 + 2 * d;
-      const int64_t cut = (int64_t)t0 - (int64_t)ra;
-      strong = strong && no.Ldl >= back &&
-               (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut);
-      no.rc = rsc;
-      no.resA = ra;
-    } else {
-      strong = strong && no.Ldl >= t0;
-    }
+    for (int k = 0; k < N; ++k) strong = strong & ((L == (uint32_t)k) | (word(HF_QMETA, k) == qm0));
+    // The round's heartbeat lth0 (none in progress: the next one) is `back` ticks before the
+    // leader's deadline: hb until it takes a response, then that response's tick
+    // (th + 2d + j0 - 1 for the j0-th) + hb.
+    const uint32_t j0 = (uint32_t)F - rsc;
+    const uint32_t back = msel(need | cutr, hb + msel(cutr & (j0 != 0), 2 * d + j0 - 1, 0u), 0u);
+    lmid = msel(need, 1u, msel(cutr, 2u, 0u));
+    lth0 = no.Ldl - back;
+    const uint32_t ta = lth0 + d, ra = lth0 + 2 * d;
+    const int64_t cut = (int64_t)t0 - (int64_t)ra;
+    const bool on_need = ta >= t0;
+    const bool on_cut = (int64_t)j0 == (cut < 0 ? 0 : cut > F ? (int64_t)F : cut);
+    const bool on_none = no.Ldl >= t0;
+    strong = strong & (no.Ldl >= back) & (need ? on_need : cutr ? on_cut : on_none);
+    no.qin = need;
+    no.qA = msel(need, ta, 0u);
+    no.rc = msel(cutr, rsc, 0u);
+    no.resA = msel(cutr, ra, INF);
     // no follower's timer fires before its next append-entries. (The followers' deadlines as
     // loaded need not be equal: set_tick or an election's exact draw may leave them apart. The
     // body never reads them again: it writes back the common re-armed one, or the words as loaded.)
-    const uint32_t nxt = min((lmid == 2 ? lth0 + P : lth0) + d, tend);   // the next AE (or end)
+    const uint32_t nxt = min(msel(cutr, lth0 + P, lth0) + d, tend);   // the next AE (or end)
 #pragma unroll
     for (int k = 0; k < N; ++k)
-      strong = strong && (L == (uint32_t)k || word(HF_DEADLINE, k) >= nxt);
+      strong = strong & ((L == (uint32_t)k) | (word(HF_DEADLINE, k) >= nxt));
+    // the band: the first heartbeat of the launch's rounds is in [t0, t0 + P) (unsigned: one
+    // before t0 fails too), so the body's rounds() has K from one comparison. A cluster outside
+    // it (set_tick moved the clock) sends its wave to the two-line path, which runs any K.
+    strong = strong & (msel(lmid != 0, lth0 + P, lth0) - t0 < P);
   }
   const bool line0_wave = !__builtin_amdgcn_ballot_w64(active && !strong);   // uniform
   if (line0_wave) {
@@ -661,7 +719,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
 #endif
     if (active) {
-      run_launch(no, lmid, lth0, tend, d, S.hb, S.el_base, P, bs);
+      const LaunchBand lb{t0, parked_band()};
+      run_launch(no, lmid, lth0, tend, d, hb, el_base, P, bs, lb);
       nhb = no.nhb; nae = no.nae; nar = no.nar;
 #ifdef RS_WAVELOG
       asm volatile("" ::"v"(no.Ltr), "v"(no.tr[0]), "v"(no.Ldl));
@@ -693,13 +752,13 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       // There is no old line 1 to compare with: line 0 goes through the image, and the chunks past
       // it (the head and tail arrivals of messages in flight) change only for a cluster with a
       // round in progress at the launch's start or its end -- stored from registers.
+      // Line 0 is dirty when the cluster ran an event here (an event changes a trace hash) and
+      // clean when it ran none (every word written below is then the word as loaded, or derived
+      // from it as the certificate says): no compare of the words.
 #pragma unroll
-      for (int i = (int)HOT_CW / 4; i < (CH_END < 8 ? CH_END : 8); ++i) {
-        const int q = 4 * i;
-        const uint4 x = chunk(i);
-        *lds_at<uint4>(img, img_off(lane, i)) = x;
-        dl |= (uint32_t)(x.x != w[q] || x.y != w[q + 1] || x.z != w[q + 2] || x.w != w[q + 3]);
-      }
+      for (int i = (int)HOT_CW / 4; i < (CH_END < 8 ? CH_END : 8); ++i)
+        *lds_at<uint4>(img, img_off(lane, i)) = chunk(i);
+      dl = (nhb | nae | nar) != 0;
       if (CH_END > 8 && (lmid || no.qin || no.rc)) {   // rare
         uint4* const bp = reinterpret_cast<uint4*>(S.hot + (size_t)c * HB);
 #pragma unroll
@@ -775,6 +834,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   // the rest of its state. It leaves every cluster with a strong certificate: the next launch
   // takes the line-0 path above. Any other wave takes the general path below.
   FixedPoint<N> fx;                           // (set below, by the waves that use it)
+  const LaunchBand no_band{t0, fpa::Band{0, 0, 0}};   // (FixedPoint's rounds() reads none of it)
   bool lean = false;
   if (!line0_wave) {
     lean = vouched && cfg_ok;
@@ -800,7 +860,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     lean = lean && !qm_req_cnt(Lqm) && rsc <= (uint32_t)F && !(need && rsc) &&
            (need == 0 || need == allF);
     const uint32_t ta = fword(HF_REQ_ARR, 0, L), ra = lword(HF_RES_ARR, L);
-    const Schedule sc = schedule<F>(t0, tend, d, S.hb, P, fx.Ldl, need != 0, ta, rsc, ra);
+    const Schedule sc = schedule<F>(t0, tend, d, hb, P, fx.Ldl, need != 0, ta, rsc, ra);
     lean = lean && sc.on;
     lmid = sc.mid;
     lth0 = sc.th0;
@@ -830,7 +890,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
 #endif
     if (active) {
-      run_launch(fx, lmid, lth0, tend, d, S.hb, S.el_base, P, bs);
+      run_launch(fx, lmid, lth0, tend, d, hb, el_base, P, bs, no_band);
       nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
 #ifdef RS_WAVELOG
       asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
@@ -890,7 +950,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     // election cut by the launch's end, a state that only looks like init-node -- is bailed.
     {
       auto ifield = [&](int f, int k) { return w[HOT_CW + f * N + k]; };
-      bool pat = active && w[CL_HWM_IDX] == 0 && S.Q >= 2u * F && S.el_base >= P && S.hb >= 2 * d + F;
+      bool pat = active && w[CL_HWM_IDX] == 0 && S.Q >= 2u * F && el_base >= P && hb >= 2 * d + F;
       const uint32_t T = ifield(HF_TERM, 0);
 #pragma unroll
       for (int k = 0; k < N; ++k) {
@@ -970,8 +1030,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
                                              : pack_flags(RAFT_FOLLWER, 0, cid, 0, 0, 0) | FL_DRAW;
           w[HOT_CW + HF_MASKS * N + k] = isc ? peers << 16 : 0u;
           w[HOT_CW + HF_TERM * N + k] = T1;
-          w[HOT_CW + HF_DEADLINE * N + k] = isc ? (uint32_t)tlast + S.hb
-                                                : (uint32_t)tL + d + S.el_base;   // + the owed draw
+          w[HOT_CW + HF_DEADLINE * N + k] = isc ? (uint32_t)tlast + hb
+                                                : (uint32_t)tL + d + el_base;     // + the owed draw
           w[HOT_CW + HF_REQ_TAIL * N + k] = 0;
           w[HOT_CW + HF_RES_TAIL * N + k] = 0;
           w[HOT_CW + HF_TRACE_LO * N + k] = (uint32_t)h;
@@ -1031,7 +1091,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
             const uint4 ew = event_draw(g, B, tb, S);
             take_req = !(ew.x & 1);
             bexact = true;
-            bdl = tb + S.el_base + __umulhi(ew.y, S.el_span);
+            bdl = tb + el_base + __umulhi(ew.y, S.el_span);
           }
           if (take_req) {                                     // append-entries-handler 105-123
             hbb = trace_event(hbb, tb, RAFT_MSG_APPEND_ENTRIES, A, T1, RAFT_FOLLWER, T1, 0);
@@ -1048,7 +1108,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
             hbb = trace_event(hbb, tb, RAFT_MSG_VOTE_RESPONSE, fid, T, brole, T1, 0);
             ++j;
           }
-          if (!bexact) bdl = tb + S.el_base;                  // + the owed draw
+          if (!bexact) bdl = tb + el_base;                    // + the owed draw
           ++tb;
         }
         const uint32_t tbl = tb - 1;                          // b's last event
@@ -1087,7 +1147,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
                     : pack_flags(RAFT_FOLLWER, 0, A, 0, 0, 0) | (isb && bexact ? 0u : FL_DRAW);
             w[HOT_CW + HF_MASKS * N + k] = isa ? peers << 16 : 0u;
             w[HOT_CW + HF_TERM * N + k] = T1;
-            w[HOT_CW + HF_DEADLINE * N + k] = isa ? tal + S.hb : isb ? bdl : tLt + 1 + S.el_base;
+            w[HOT_CW + HF_DEADLINE * N + k] = isa ? tal + hb : isb ? bdl : tLt + 1 + el_base;
             w[HOT_CW + HF_REQ_TAIL * N + k] = 0;
             w[HOT_CW + HF_RES_TAIL * N + k] = 0;
             w[HOT_CW + HF_TRACE_LO * N + k] = (uint32_t)h;
@@ -1241,7 +1301,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
       for (int j = 0; j < F; ++j) {
         if ((due >> j) & 1) {
-          const uint4 wd = event_draw(g, fx.fk(j) + 1, fx.fdl[j] - S.el_base, S);   // D4, core.clj:174
+          const uint4 wd = event_draw(g, fx.fk(j) + 1, fx.fdl[j] - el_base, S);   // D4, core.clj:174
           fx.fdl[j] += __umulhi(wd.y, S.el_span);
         }
       }
@@ -1271,9 +1331,9 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       return ok;
     };
     auto at_fixed_point = [&]() {
-      return S.el_base >= P && S.hb >= 2 * d + F && !fx.qmask && !fx.rmask && at_fixed_point_state();
+      return el_base >= P && hb >= 2 * d + F && !fx.qmask && !fx.rmask && at_fixed_point_state();
     };
-    auto fixed_point_rounds = [&](uint32_t th) { rounds(fx, th, tend, d, S.hb, S.el_base, bs); };
+    auto fixed_point_rounds = [&](uint32_t th) { rounds(fx, th, tend, d, hb, el_base, bs, no_band); };
 
     // ------------------------------------------- the fixed-point path (C2's steady state)
     // A cluster at its fixed point (above) whose round in progress at t0 is on the period-P
@@ -1281,9 +1341,9 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     // responses pending exactly as the last launch's end cut them -- and whose followers' timers
     // cannot fire before their next append-entries runs every event of the launch here: the rest
     // of that round, then the rounds (run_launch). Everything else is the general loop's.
-    bool fp = wb && S.el_base >= P && S.hb >= 2 * d + F && (vouched || at_fixed_point_state());
+    bool fp = wb && el_base >= P && hb >= 2 * d + F && (vouched || at_fixed_point_state());
     // (the round's heartbeat th0; mid: 1 append-entries in flight, 2 responses)
-    const Schedule sc = schedule<F>(t0, tend, d, S.hb, P, fx.Ldl, fx.qmask != 0, fx.qA[0],
+    const Schedule sc = schedule<F>(t0, tend, d, hb, P, fx.Ldl, fx.qmask != 0, fx.qA[0],
                                     __popc(fx.rmask), fx.resA);
     const uint32_t th0 = sc.th0, mid = sc.mid;
     fp = fp && sc.on;
@@ -1312,7 +1372,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #endif
     if (fp) {
       run = false;
-      run_launch(fx, mid, th0, tend, d, S.hb, S.el_base, P, bs);
+      run_launch(fx, mid, th0, tend, d, hb, el_base, P, bs, no_band);
     }
 #ifdef RS_WAVELOG
     asm volatile("" ::"v"(fx.Ltr), "v"(fx.ftr[0]), "v"(fx.Ldl));
@@ -1399,7 +1459,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
           fx.qb[j] = nx[j] - 1 > 0 ? (uint32_t)(nx[j] - 1) : 0u;
         }
         fx.qmask = (1u << F) - 1;
-        fx.Ldl = t + S.hb;
+        fx.Ldl = t + hb;
         fx.Ltr = trace_event(fx.Ltr, t, 7, 0, 0, RAFT_LEADER, Lterm, 0);
         ++fx.nhb;
         // The whole heartbeat round in this trip when nothing else can happen before its last
@@ -1410,7 +1470,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         // responses then run in slot order up to the launch end (the rest stay queued) and stop at
         // one outside the model (the next trip decides it). A deferred deadline counts with its
         // lower bound here (a round not taken is run tick by tick).
-        round = fx.rmask == 0 && S.hb >= 2 * d + F && S.el_base >= d + F && tend - t > d;
+        round = fx.rmask == 0 && hb >= 2 * d + F && el_base >= d + F && tend - t > d;
 #pragma unroll
         for (int j = 0; j < F; ++j)
           round = round && fx.fdl[j] >= t + d && fx.qb[j] == 0 &&
@@ -1442,7 +1502,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
             // the response: to the leader's RES queue, in sender id order
             fx.rT[j] = rterm; fx.rA[j] = ok ? fx.qa[j] : 0u; fx.rB[j] = 0; fx.rH[j] = ok;
             fx.qA[j] = INF;
-            fx.fdl[j] = ta + S.el_base;                           // + the deferred draw
+            fx.fdl[j] = ta + el_base;                             // + the deferred draw
           }
         }
         fx.fpend |= fa;
@@ -1463,7 +1523,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
         Lmk |= yH << (16 + yid);
         nxj = yH ? (int32_t)yB : nxj - 1;
         mtj = yH ? (int32_t)yA : mtj;
-        fx.Ldl = tau + S.hb;
+        fx.Ldl = tau + hb;
         fx.Ltr = trace_event(fx.Ltr, tau, RAFT_MSG_APPEND_RESPONSE, yid, yT, RAFT_LEADER, Lterm, 0);
         ++fx.nar;
         tl = tau;
@@ -1647,11 +1707,27 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
       for (int gq = 0; gq < 8; ++gq)
         xs[gq] = *lds_at<const uint4>(img, img_off(8 * gq + sub, 8 * ln + q8));
+      typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+      if (bal == ~0ull) {
+        // every cluster of a full wave (the headline's every wave): eight stores with no
+        // predicate, a lane's address in the first group of eight blocks once and one 64-bit add
+        // per further group. (Addresses stay in vector registers: a store in an asm statement
+        // that took its base from scalar registers would stand outside the compiler's hazard
+        // checks, and a scalar register a vector instruction wrote needs five wait states
+        // before a memory instruction reads it.)
+        uint32_t* const dst0 = wbase + sub * HB + 4 * (8 * ln + q8);
+#pragma unroll
+        for (int gq = 0; gq < 8; ++gq) {
+          const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
+          uint32_t* const dst = dst0 + (size_t)(8 * gq) * HB;
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
+        }
+        continue;
+      }
 #pragma unroll
       for (int gq = 0; gq < 8; ++gq) {
         const uint32_t cc = 8 * gq + sub;
         if ((bal >> cc) & 1) {
-          typedef uint32_t v4u __attribute__((ext_vector_type(4)));
           const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
           uint32_t* const dst = wbase + cc * HB + 4 * (8 * ln + q8);
           asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
@@ -1688,12 +1764,16 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     const uint32_t h = wave_sum(nhb), a = wave_sum(nae), r = wave_sum(nar);
     unsigned long long* const ctr =
         S.ctr + (size_t)((blockIdx.x * 4 + wave) % CTR_COPIES) * CTR_STRIDE;
-    if (lane < 5) {
+    {
+      // lane 0 .. 4: heartbeats, append-entries, append-responses, sent, delivered. The index is
+      // a nibble of a constant and the value a chain of selects: one branch, around the atomic.
+      constexpr uint32_t IDX = RAFT_CTR_EV_HEARTBEAT | RAFT_CTR_EV_AE << 4 | RAFT_CTR_EV_AR << 8 |
+                               RAFT_CTR_SENT << 12 | RAFT_CTR_DELIVERED << 16;
+      static_assert(RAFT_CTR_DELIVERED < 16, "a nibble per index");
       const uint32_t msgs = (uint32_t)F * h + a;
-      const int idx = lane == 0 ? RAFT_CTR_EV_HEARTBEAT : lane == 1 ? RAFT_CTR_EV_AE
-                    : lane == 2 ? RAFT_CTR_EV_AR : lane == 3 ? RAFT_CTR_SENT : RAFT_CTR_DELIVERED;
-      const uint32_t v = lane == 0 ? h : lane == 1 ? a : lane == 2 ? r : msgs;
-      if (v) atomicAdd(&ctr[idx], (unsigned long long)v);
+      const uint32_t idx = (IDX >> (4 * (lane & 7))) & 15u;
+      const uint32_t v = msel(lane == 0, h, msel(lane == 1, a, msel(lane == 2, r, msgs)));
+      if (lane < 5 && v) atomicAdd(&ctr[idx], (unsigned long long)v);
     }
     if (__builtin_amdgcn_ballot_w64(el)) {                   // wave-uniform
       // per election: el_to timeouts, F request-votes and F vote responses per timeout, one
