@@ -284,6 +284,43 @@
                       :commit-diverged (ids (.getShort m (+ r 26)))
                       :len-min (.getInt m (+ r 28))}))}))
 
+;; raft_gather_layout_t (104 bytes, 13 u64): stride 0, off[6] 8, size[6] 56. No reference
+;; counterpart: the full state of a list of clusters, packed on the device.
+(def gather-layout-size 104)
+(def gather-parts
+  {:cluster 1 :nodes 2 :queues 4 :logs 8 :arenas 16 :streams 32})
+(def ^:private gather-part-order [:cluster :nodes :queues :logs :arenas :streams])
+
+(defn gather-layout
+  "Where the parts (a subset of the keys of gather-parts) stand in a cluster's record
+  (raft_gather_layout): {:stride bytes, part {:off o :size s}} for the parts asked for."
+  [sim parts]
+  (let [m (Memory. gather-layout-size)
+        mask (int (reduce bit-or 0 (map gather-parts parts)))]
+    (call "raft_gather_layout" (:ptr sim) mask m)
+    (into {:stride (.getLong m 0)}
+          (for [[b k] (map-indexed vector gather-part-order)
+                :let [off (.getLong m (+ 8 (* 8 b)))]
+                :when (not= off -1)]                    ; UINT64_MAX: not asked for
+            [k {:off off :size (.getLong m (+ 56 (* 8 b)))}]))))
+
+(defn gather
+  "The full state of the clusters `cs` (handle-local indices, any order) packed on the device
+  (raft_gather_read): {:layout (gather-layout sim parts) :buffer m}, record i of the Memory m
+  being cluster (nth cs i) at byte (* i stride). :nodes carries the counts of the other parts."
+  [sim cs parts]
+  (let [layout (gather-layout sim parts)
+        n (count cs)
+        bytes (* n (:stride layout))
+        idx (Memory. (* 4 (max 1 n)))
+        m (Memory. (max 1 bytes))
+        mask (int (reduce bit-or 0 (map gather-parts parts)))]
+    (doseq [[i c] (map-indexed vector cs)] (.setInt idx (* 4 i) (unchecked-int c)))
+    (let [rc (.invokeLong (f "raft_gather_read")
+                          (object-array [(:ptr sim) idx (int n) mask m (long bytes)]))]
+      (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
+      {:layout layout :buffer m})))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

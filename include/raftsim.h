@@ -401,6 +401,50 @@ int raft_audit_read(raft_sim_t* sim, raft_audit_t* out);
 int64_t raft_audit_select(raft_sim_t* sim, uint32_t any_mask, uint32_t all_mask,
                           uint32_t none_mask, raft_audit_record_t* out, uint32_t cap);
 
+/* ---- Cluster packs (no reference counterpart, none in the oracle) ---------------------------
+ * The full canonical state of an arbitrary list of clusters, packed on the device into one
+ * contiguous buffer of fixed-size records and copied once per device: what the per-node reads
+ * above return one synchronous copy at a time, for the clusters a selection found. A record is the
+ * parts asked for, in bit order, each starting on a 16-byte boundary (padding bytes are zero);
+ * parts not asked for take no room. The counts of a node's queues, log and commit stream are in
+ * its node record (req_count, res_count, log_len, commit_count), so RAFT_GATHER_NODES belongs in
+ * every pack that is to be decoded. A pack is a view of the state the digest covers, not state
+ * (SIM_SPEC.md §6): one cluster's record holds everything the raft_sim_write_* calls need to
+ * restore it in another handle. */
+enum raft_gather_part {
+  RAFT_GATHER_CLUSTER = 1,  /* raft_cluster_t, reserved words zero (as read_clusters returns it) */
+  RAFT_GATHER_NODES   = 2,  /* N raft_node_t, byte-identical to what read_nodes returns */
+  RAFT_GATHER_QUEUES  = 4,  /* per node REQ then RES: inbox_cap raft_msg_t, head first, zero past count */
+  RAFT_GATHER_LOGS    = 8,  /* per node log_cap raft_entry_t: entry p from slot (arena_base+p) mod A, zero past log_len */
+  RAFT_GATHER_ARENAS  = 16, /* per node the raw arena, arena_cap raft_entry_t (what read_arena copies) */
+  RAFT_GATHER_STREAMS = 32  /* per node commit_stream_cap u32: newest min(commit_count, cap), oldest first, zero past */
+};
+#define RAFT_GATHER_ALL 63
+
+typedef struct raft_gather_layout {   /* every field uint64_t */
+  uint64_t stride;        /* bytes per cluster, a multiple of 16 */
+  uint64_t off[6];        /* byte offset of part bit b in a cluster's record; UINT64_MAX: not asked for */
+  uint64_t size[6];       /* its unpadded size in bytes (0: not asked for) */
+} raft_gather_layout_t;
+
+/* The layout of a record of `parts` (raft_gather_part bits, 1..RAFT_GATHER_ALL) in this handle: a
+ * function of its config and `parts` alone. RAFT_GATHER_STREAMS has size 0 when commit_stream_cap
+ * is 0; a log_len above log_cap is clamped to it in RAFT_GATHER_LOGS. -EINVAL: null argument,
+ * parts 0 or above RAFT_GATHER_ALL. Touches no device. */
+int raft_gather_layout(raft_sim_t* sim, uint32_t parts, raft_gather_layout_t* out);
+
+/* Record i of out is cluster clusters[i] (handle-local indices, in any order, with duplicates,
+ * across devices); returns n * stride, the bytes written. -EINVAL: null sim, parts 0 or above
+ * RAFT_GATHER_ALL, null clusters or out with n > 0, an index >= n_clusters (the message names the
+ * first offending position); -ERANGE: cap_bytes < n * stride; all refused before any device is
+ * touched. -EIO: a HIP error, or a handle poisoned by a failed step. n == 0 returns 0 and launches
+ * nothing. The packing runs on the device, stream-ordered after everything enqueued (valid after
+ * raft_sim_step_async, which it waits for), and reads the state only: digest, counters, violation
+ * records, the audit's records and a steady certificate stay, and the next step runs as it would
+ * have. Device scratch is bounded (64 MiB per device); larger requests run in chunks. */
+int64_t raft_gather_read(raft_sim_t* sim, const uint32_t* clusters, uint32_t n, uint32_t parts,
+                         void* out, uint64_t cap_bytes);
+
 #ifdef __cplusplus
 }
 #endif

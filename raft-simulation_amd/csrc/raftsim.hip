@@ -37,6 +37,9 @@ hipError_t launch_audit(const DevSim& S, uint32_t width, void* rec, unsigned lon
 hipError_t launch_audit_select(uint32_t C, uint32_t any, uint32_t all, uint32_t none,
                                const void* rec, unsigned long long* scratch, void* out,
                                uint32_t cap, hipStream_t st);
+// gather_kernel.hip
+hipError_t launch_gather(const DevSim& S, const void* pairs, uint32_t n,
+                         const raft_gather_layout_t& Y, void* out, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -132,6 +135,14 @@ struct Shard {
   unsigned long long* ascratch;
   bool audit_valid;
   double audit_ms;
+  // raft_gather_read (gather_kernel.hip): the device scratch its records are packed into and the
+  // (cluster, slot) list behind them in the same allocation, made and grown by the queries up to
+  // GATHER_SCRATCH_BYTES; an event pair per chunk of a query; the device time of the last query's
+  // kernels (raftsim_diag_gather_ms).
+  uint8_t* gscratch;
+  size_t gscratch_bytes;
+  std::vector<hipEvent_t> gev;
+  double gather_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
 // The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
@@ -218,6 +229,8 @@ static void sh_destroy(Shard* s) {
   if (s->qev0) (void)hipEventDestroy(s->qev0);
   if (s->qev1) (void)hipEventDestroy(s->qev1);
   for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : s->gev) (void)hipEventDestroy(e);
+  if (s->gscratch) (void)hipFree(s->gscratch);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1387,6 +1400,179 @@ int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, u
 // compaction's alone.
 extern "C" int raftsim_diag_audit_ms(raft_sim_t* r, double* ms) {
   return diag_ms(r, ms, &Shard::audit_ms);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cluster packs (include/raftsim.h, "no reference counterpart, none in the oracle"): a read-only
+// kernel over the state of a list of clusters on every shard's stream at once, behind whatever the
+// shard has enqueued. The caller's list is split by owner shard; a shard packs its clusters into
+// its scratch, GATHER_SCRATCH_BYTES at a time, and every chunk is one device-to-host copy: straight
+// into the caller's buffer where the shard's clusters stand at consecutive positions of the list
+// (always, on one device), else into a host buffer whose records are moved to their positions once
+// the shard is done. Like the census it touches neither the state nor the host's bookkeeping of it
+// (storm_until, keys_written, lite, audit_valid, the steady path choice).
+constexpr uint64_t GATHER_SCRATCH_BYTES = 64ull << 20;
+
+static void gather_layout_of(const Shard* s, uint32_t parts, raft_gather_layout_t* y) {
+  const uint64_t N = s->N;
+  const uint64_t size[6] = {sizeof(raft_cluster_t),
+                            N * sizeof(raft_node_t),
+                            N * 2 * s->Q * sizeof(raft_msg_t),
+                            N * s->L * sizeof(raft_entry_t),
+                            N * s->A * sizeof(raft_entry_t),
+                            N * s->cfg.commit_stream_cap * sizeof(uint32_t)};
+  uint64_t off = 0;
+  for (int b = 0; b < 6; ++b) {
+    const bool on = (parts >> b) & 1;
+    y->off[b] = on ? off : UINT64_MAX;
+    y->size[b] = on ? size[b] : 0;
+    if (on) off += (size[b] + 15) & ~15ull;
+  }
+  y->stride = off;
+}
+
+static int gather_parts_ok(uint32_t parts) {
+  if (parts == 0 || parts > RAFT_GATHER_ALL)
+    return fail(-EINVAL, "parts must be 1..RAFT_GATHER_ALL (63)");
+  return 0;
+}
+
+int raft_gather_layout(raft_sim_t* r, uint32_t parts, raft_gather_layout_t* out) {
+  if (!r || !out) return fail(-EINVAL, "null argument");
+  const int rc = gather_parts_ok(parts);
+  if (rc) return rc;
+  gather_layout_of(r->sh[0], parts, out);
+  return 0;
+}
+
+// One shard's share of a raft_gather_read.
+struct GatherJob {
+  std::vector<uint2> pairs;     // (shard-local cluster, slot in its chunk's scratch)
+  std::vector<uint32_t> pos;    // the record's position in the caller's list
+  std::vector<uint8_t> stage;   // the shard's records in list order, unless they go straight to out
+  uint8_t* host = nullptr;      // where chunk 0's first record goes
+  uint32_t per_chunk = 0, chunks = 0;
+};
+
+int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, uint32_t parts,
+                         void* out, uint64_t cap_bytes) {
+  if (!r) return fail(-EINVAL, "null sim");
+  int rc = gather_parts_ok(parts);
+  if (rc) return rc;
+  if (n && !clusters) return fail(-EINVAL, "null cluster list");
+  if (n && !out) return fail(-EINVAL, "null output");
+  for (uint32_t i = 0; i < n; ++i)
+    if (clusters[i] >= r->cfg.n_clusters) {
+      char what[96];
+      snprintf(what, sizeof what, "clusters[%u] = %u is outside the handle's %u clusters", i,
+               clusters[i], r->cfg.n_clusters);
+      return fail(-EINVAL, "%s", what);
+    }
+  raft_gather_layout_t Y;
+  gather_layout_of(r->sh[0], parts, &Y);
+  const uint64_t stride = Y.stride, bytes = (uint64_t)n * stride;   // stride < 2^31: no overflow
+  if (cap_bytes < bytes) return fail(-ERANGE, "cap_bytes is below n * stride");
+  if (r->poisoned) return unusable();
+  if (!bytes) return 0;          // no cluster, or the commit streams alone of a handle without them
+
+  const size_t G = r->sh.size();
+  std::vector<GatherJob> job(G);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t c = clusters[i];
+    const size_t d = G == 1 ? 0 : std::upper_bound(r->lo.begin() + 1, r->lo.end() - 1, c) -
+                                      (r->lo.begin() + 1);
+    job[d].pairs.push_back(make_uint2(c - r->lo[d], 0));
+    job[d].pos.push_back(i);
+  }
+  // records and their list entries share the scratch: stride + 8 bytes each, one record at least
+  const uint32_t per_chunk =
+      (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(GATHER_SCRATCH_BYTES / (stride + 8), n));
+  uint8_t* const dst = static_cast<uint8_t*>(out);
+  auto step = [&](hipError_t e) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_gather_read: %s",
+                                          hipGetErrorString(e));
+    return !rc;
+  };
+  size_t started = 0;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    Shard* s = r->sh[d];
+    GatherJob& j = job[d];
+    const size_t m = j.pairs.size();
+    ++started;
+    if (!m) continue;
+    bool direct = true;
+    for (size_t i = 1; i < m && direct; ++i) direct = j.pos[i] == j.pos[0] + i;
+    if (direct) j.host = dst + (size_t)j.pos[0] * stride;
+    else {
+      j.stage.resize(m * stride);
+      j.host = j.stage.data();
+    }
+    j.per_chunk = (uint32_t)std::min<size_t>(per_chunk, m);
+    j.chunks = (uint32_t)((m + j.per_chunk - 1) / j.per_chunk);
+    for (size_t i = 0; i < m; ++i) j.pairs[i].y = (uint32_t)(i % j.per_chunk);
+    if (!step(hipSetDevice(s->cfg.device))) break;
+    const size_t need = (size_t)j.per_chunk * (stride + 8);
+    if (s->gscratch_bytes < need) {
+      if (!step(hipStreamSynchronize(s->stream))) break;
+      if (s->gscratch) (void)hipFree(s->gscratch);
+      s->gscratch = nullptr;
+      s->gscratch_bytes = 0;
+      void* v = nullptr;
+      const hipError_t e = hipMalloc(&v, need);
+      if (e != hipSuccess) {
+        rc = fail(-ENOMEM, "hipMalloc failed in raft_gather_read: %s", hipGetErrorString(e));
+        break;
+      }
+      s->gscratch = static_cast<uint8_t*>(v);
+      s->gscratch_bytes = need;
+    }
+    while (!rc && s->gev.size() < 2 * (size_t)j.chunks) {
+      hipEvent_t e;
+      if (step(hipEventCreate(&e))) s->gev.push_back(e);
+    }
+    // the list stands behind the records (stride is a multiple of 16)
+    uint2* const dpairs = reinterpret_cast<uint2*>(s->gscratch + (size_t)j.per_chunk * stride);
+    for (uint32_t ch = 0; ch < j.chunks && !rc; ++ch) {
+      const size_t i0 = (size_t)ch * j.per_chunk;
+      const uint32_t k = (uint32_t)std::min<size_t>(j.per_chunk, m - i0);
+      step(h2d(s, dpairs, j.pairs.data() + i0, k)) &&
+          step(hipEventRecord(s->gev[2 * ch], s->stream)) &&
+          step(rs::launch_gather(s->d, dpairs, k, Y, s->gscratch, s->stream)) &&
+          step(hipEventRecord(s->gev[2 * ch + 1], s->stream)) &&
+          step(hipMemcpyAsync(j.host + i0 * stride, s->gscratch, (size_t)k * stride,
+                              hipMemcpyDeviceToHost, s->stream));
+    }
+  }
+  // every started shard is waited for, also after an error: its copies write out and the stages
+  for (size_t d = 0; d < started; ++d) {
+    Shard* s = r->sh[d];
+    GatherJob& j = job[d];
+    if (j.pairs.empty()) {
+      if (!rc) s->gather_ms = 0;
+      continue;
+    }
+    step(hipSetDevice(s->cfg.device));
+    step(hipStreamSynchronize(s->stream));
+    if (rc) continue;
+    double ms = 0;
+    for (uint32_t ch = 0; ch < j.chunks && !rc; ++ch) {
+      float t = 0;
+      if (step(hipEventElapsedTime(&t, s->gev[2 * ch], s->gev[2 * ch + 1]))) ms += t;
+    }
+    if (rc) continue;
+    s->gather_ms = ms;
+    if (!j.stage.empty())
+      for (size_t i = 0; i < j.pos.size(); ++i)
+        memcpy(dst + (size_t)j.pos[i] * stride, j.stage.data() + i * stride, stride);
+  }
+  return rc ? rc : (int64_t)bytes;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_gather_read's kernels
+// (HIP events around each chunk's kernel on each shard's stream, summed), the maximum over shards,
+// in ms.
+extern "C" int raftsim_diag_gather_ms(raft_sim_t* r, double* ms) {
+  return diag_ms(r, ms, &Shard::gather_ms);
 }
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was

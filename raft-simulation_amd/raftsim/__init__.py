@@ -13,7 +13,8 @@ from pathlib import Path
 
 from . import _build
 from ._abi import COUNTER_NAMES  # noqa: F401
-from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, GpuBackend,  # noqa: F401
+from . import _abi
+from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, ClusterPack, GpuBackend,  # noqa: F401
                        RaftSimError, replay_config)
 
 PKG_DIR = Path(__file__).resolve().parent.parent          # raft-simulation_amd/
@@ -98,4 +99,29 @@ def replay(sim, cluster, ticks=None):
     # (results do not depend on the step size; one step runs ticks_per_launch ticks per launch)
     if ticks:
         one.step(ticks)
+    return one
+
+
+def fork(source, cluster, **overrides):
+    """A one-cluster Simulator that continues one cluster from a snapshot instead of rerunning it.
+    `source` is a Simulator, whose cluster `cluster` is gathered with every part, or a ClusterPack
+    (gather(), ClusterPack.load), of which `cluster` is the position in the pack. The new handle
+    has the source's config with n_clusters=1 at the cluster's global id and the trace rings on
+    (replay_config; `overrides` replace any field, e.g. trace_cap=0, trace_entry_cap=0), and is
+    restored through restore_cluster: it starts at the pack's tick with the digest the cluster had
+    there and continues bit-exactly as the cluster does in its source.
+
+    Unlike replay(), fork works on handles the host has written (write_*, set_tick), and costs the
+    snapshot, not the run so far. What it does not carry over, because neither is state: the
+    fork's trace `seq` numbers (and entries_seq) start at 0 at the pack's tick, and its violation
+    records start empty -- violations() of the fork reports what happens from the pack's tick on."""
+    if isinstance(source, ClusterPack):
+        pack, i = source, int(cluster)
+        if not 0 <= i < len(pack):
+            raise ValueError(f"position {i} outside the pack's {len(pack)} clusters")
+    else:
+        pack, i = source.gather([cluster]), 0
+    cfg = replay_config(_abi.Config(**pack.config), pack.clusters[i], **overrides)
+    one = Simulator(**cfg)
+    one.restore_cluster(pack, i)
     return one

@@ -263,6 +263,49 @@ _AUDIT_SIGS = {
 AUDIT_SYMBOLS = ["raft_audit_" + n for n in _AUDIT_SIGS]
 
 
+# raft_gather_part bits (include/raftsim.h, "Cluster packs"), in the order of a record's parts
+GATHER_PARTS = {"cluster": 1, "nodes": 2, "queues": 4, "logs": 8, "arenas": 16, "streams": 32}
+GATHER_ALL = 63
+
+
+class GatherLayout(C.Structure):
+    """raft_gather_layout_t: where a pack's parts stand in a cluster's record."""
+    _fields_ = [("stride", C.c_uint64), ("off", C.c_uint64 * 6), ("size", C.c_uint64 * 6)]
+
+    def as_dict(self):
+        """{"stride": bytes per cluster, part name: (offset, size) for the parts asked for}."""
+        d = {"stride": int(self.stride)}
+        for b, name in enumerate(GATHER_PARTS):
+            if self.off[b] != _NONE64:
+                d[name] = (int(self.off[b]), int(self.size[b]))
+        return d
+
+
+def gather_layout(nodes, inbox_cap, log_cap, arena_cap, commit_stream_cap, parts):
+    """raft_gather_layout's answer for a config, as GatherLayout.as_dict gives it (needs no
+    library): parts in bit order, each on a 16-byte boundary, absent parts take no room."""
+    A = arena_cap or 4 * log_cap
+    sizes = (C.sizeof(Cluster), nodes * C.sizeof(Node), nodes * 2 * inbox_cap * C.sizeof(Msg),
+             nodes * log_cap * C.sizeof(Entry), nodes * A * C.sizeof(Entry),
+             nodes * commit_stream_cap * 4)
+    d, off = {}, 0
+    for (name, bit), size in zip(GATHER_PARTS.items(), sizes):
+        if parts & bit:
+            d[name] = (off, size)
+            off += (size + 15) & ~15
+    return dict(stride=off, **d)
+
+
+# Cluster packs, like the audit, have no oracle counterpart: bound for the product library only,
+# under their own prefix.
+_GATHER_SIGS = {
+    "layout": (C.c_int, [C.c_void_p, C.c_uint32, P(GatherLayout)]),
+    "read": (C.c_int64, [C.c_void_p, P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_void_p,
+                         C.c_uint64]),
+}
+GATHER_SYMBOLS = ["raft_gather_" + n for n in _GATHER_SIGS]
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

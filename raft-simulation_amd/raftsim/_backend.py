@@ -26,6 +26,137 @@ def make_config(fns, **kw) -> _abi.Config:
     return cfg
 
 
+def _npz(path):
+    path = str(path)
+    return path if path.endswith(".npz") else path + ".npz"
+
+
+class ClusterPack:
+    """The full canonical state of some clusters of a handle at one tick, as raft_gather_read
+    packed it (include/raftsim.h, "Cluster packs"): one numpy.uint8 buffer of len(clusters)
+    records of `layout["stride"]` bytes, and what is needed to read it without the handle.
+
+      config    the source handle's config, a dict of raft_sim_config_t fields
+      tick      the source handle's tick when the pack was taken
+      clusters  the handle-local ids of the packed clusters, in record order; global_ids adds
+                the config's cluster_offset
+      layout    {"stride": bytes, part name: (offset, size)} for the parts the pack holds
+      data      the records
+
+    The accessors take the position `i` of a cluster in the pack and return views of `data` or
+    plain Python values decoded from them; none of them copies a part."""
+
+    def __init__(self, config, tick, clusters, layout, data):
+        self.config = dict(config)
+        self.tick = int(tick)
+        self.clusters = [int(c) for c in clusters]
+        self.layout = {k: (int(v) if k == "stride" else (int(v[0]), int(v[1])))
+                       for k, v in layout.items()}
+        self.data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if self.data.size != len(self.clusters) * self.layout["stride"]:
+            raise ValueError("the buffer is not len(clusters) * stride bytes")
+        self.N = self.config["nodes"]
+        self.Q = self.config["inbox_cap"]
+        self.L = self.config["log_cap"]
+        self.A = self.config["arena_cap"] or 4 * self.L
+        self.SC = self.config["commit_stream_cap"]
+        self.nodes = _PackNodes(self)
+
+    def __len__(self):
+        return len(self.clusters)
+
+    @property
+    def parts(self):
+        return tuple(k for k in _abi.GATHER_PARTS if k in self.layout)
+
+    @property
+    def global_ids(self):
+        return [self.config["cluster_offset"] + c for c in self.clusters]
+
+    def part(self, i, name):
+        """The bytes of part `name` of the pack's i-th cluster (a view)."""
+        if name not in self.layout:
+            raise ValueError(f"the pack holds no {name!r} part (it has {list(self.parts)})")
+        if not 0 <= i < len(self.clusters):
+            raise IndexError(f"position {i} outside the pack's {len(self.clusters)} clusters")
+        off, size = self.layout[name]
+        at = i * self.layout["stride"] + off
+        return self.data[at:at + size]
+
+    def _node(self, i, node_id):
+        if not 1 <= node_id <= self.N:
+            raise IndexError(f"node id {node_id} outside 1..{self.N}")
+        return self.nodes[i][node_id - 1]
+
+    def node_dicts(self, i):
+        """The cluster's node records as read_nodes gives them."""
+        return [n.as_dict(self.N) for n in self.nodes[i]]
+
+    def cluster(self, i):
+        """The cluster record as read_clusters gives it."""
+        return _abi.Cluster.from_buffer(self.part(i, "cluster")).as_dict()
+
+    def queue(self, i, node_id, which):
+        """The messages of the node's req (which=0) or resp (1) queue, head first, as 8-word
+        tuples (what read_queue gives)."""
+        n = self._node(i, node_id)
+        cnt = min(n.res_count if which else n.req_count, self.Q)
+        q = self.part(i, "queues").view(np.uint32).reshape(self.N, 2, self.Q, 8)
+        return [tuple(m) for m in q[node_id - 1, which, :cnt].tolist()]
+
+    def log(self, i, node_id):
+        """The node's logical log as (term, val) tuples (what Backend.log gives)."""
+        n = min(self._node(i, node_id).log_len, self.L)
+        lg = self.part(i, "logs").view(np.uint32).reshape(self.N, self.L, 2)
+        return [tuple(e) for e in lg[node_id - 1, :n].tolist()]
+
+    def arena(self, i, node_id):
+        """The node's raw log arena as (term, val) tuples (what read_arena gives)."""
+        self._node(i, node_id)
+        ar = self.part(i, "arenas").view(np.uint32).reshape(self.N, self.A, 2)
+        return [tuple(e) for e in ar[node_id - 1].tolist()]
+
+    def commit_stream(self, i, node_id):
+        """The newest committed values the ring retains, oldest first (what commit_stream gives)."""
+        kept = min(self._node(i, node_id).commit_count, self.SC)
+        if not self.SC:
+            self.part(i, "streams")
+            return []
+        st = self.part(i, "streams").view(np.uint32).reshape(self.N, self.SC)
+        return st[node_id - 1, :kept].tolist()
+
+    def save(self, path):
+        """Write the pack to one .npz file (numpy arrays and a JSON string; no pickle)."""
+        import json
+        meta = json.dumps({"config": self.config, "tick": self.tick, "layout": self.layout})
+        np.savez(_npz(path), data=self.data, clusters=np.asarray(self.clusters, dtype=np.uint32),
+                 meta=np.asarray(meta))
+        return _npz(path)
+
+    @classmethod
+    def load(cls, path):
+        import json
+        with np.load(_npz(path), allow_pickle=False) as z:
+            meta = json.loads(str(z["meta"]))
+            return cls(meta["config"], meta["tick"], z["clusters"].tolist(), meta["layout"],
+                       z["data"])
+
+
+class _PackNodes:
+    """pack.nodes: nodes[i] is the i-th cluster's N raft_node_t as an _abi.Node array over the
+    pack's bytes (nodes[i][k] is node id k + 1)."""
+
+    def __init__(self, pack):
+        self._pack = pack
+
+    def __len__(self):
+        return len(self._pack.clusters)
+
+    def __getitem__(self, i):
+        p = self._pack
+        return (_abi.Node * p.N).from_buffer(p.part(i, "nodes"))
+
+
 class Backend:
     """One simulator handle. `lib_path` + `prefix` select the implementation."""
 
@@ -249,6 +380,40 @@ class Backend:
                                         out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
 
+    def restore_cluster(self, pack, i, cluster=0):
+        """Make cluster `cluster` of this handle the pack's i-th cluster at the pack's tick, through
+        the write_* calls: set_tick (the whole handle's clock), write_nodes, write_clusters, every
+        write_arena, every write_queue, then every write_commit_stream. The handle must have the
+        pack's nodes, log_cap, arena_cap, inbox_cap and commit_stream_cap; for the cluster to go on
+        as it would have in its source, also its timers, rates and seed, and cluster_offset +
+        cluster equal to the packed cluster's global id (replay_config gives such a config).
+        Needs the parts cluster, nodes, queues and arenas, and streams when commit_stream_cap > 0:
+        ValueError names a missing one."""
+        need = ["cluster", "nodes", "queues", "arenas"] + (["streams"] if pack.SC else [])
+        for name in need:
+            if name not in pack.layout:
+                raise ValueError(f"restore_cluster needs the {name!r} part; the pack holds "
+                                 f"{list(pack.parts)}")
+        A = self.config.arena_cap or 4 * self.config.log_cap
+        mine = (self.N, self.config.inbox_cap, self.config.log_cap, A,
+                self.config.commit_stream_cap)
+        if mine != (pack.N, pack.Q, pack.L, pack.A, pack.SC):
+            raise ValueError("restore_cluster: the handle's nodes, inbox_cap, log_cap, arena_cap, "
+                             f"commit_stream_cap {mine} are not the pack's "
+                             f"{(pack.N, pack.Q, pack.L, pack.A, pack.SC)}")
+        ids = range(1, self.N + 1)
+        self.set_tick(pack.tick)
+        self.write_nodes(cluster, list(pack.nodes[i]))
+        self.write_clusters(cluster, [pack.cluster(i)])
+        for k in ids:
+            self.write_arena(cluster, k, pack.arena(i, k))
+        for k in ids:
+            for which in (0, 1):
+                self.write_queue(cluster, k, which, pack.queue(i, k, which))
+        if pack.SC:
+            for k in ids:
+                self.write_commit_stream(cluster, k, pack.commit_stream(i, k))
+
     # -- reference vocabulary -------------------------------------------------------------------
     def node_map(self, cluster, node_id):
         """The node as the reference's `prn node` would show it (core.clj:31-38,182-183)."""
@@ -277,13 +442,15 @@ class GpuBackend(Backend):
     invariant, when first -- and the config that replays one of them alone; and ("State census")
     what state the clusters are in now, counted and selected on the device; and ("Log audit")
     whether the nodes' logs agree as they stand, and whether they disagree below the commit
-    indices."""
+    indices; and ("Cluster packs") the full state of the clusters such a query selected, packed
+    on the device into a ClusterPack."""
 
     def __init__(self, lib_path, prefix, **config):
         super().__init__(lib_path, prefix, **config)
         self._viol = _abi.bind(self._lib, "raft_viol_", sigs=_abi._VIOL_SIGS)
         self._census = _abi.bind(self._lib, "raft_census_", sigs=_abi._CENSUS_SIGS)
         self._audit = _abi.bind(self._lib, "raft_audit_", sigs=_abi._AUDIT_SIGS)
+        self._gather = _abi.bind(self._lib, "raft_gather_", sigs=_abi._GATHER_SIGS)
 
     # -- what the three device-side queries share ------------------------------------------------
     @staticmethod
@@ -435,6 +602,49 @@ class GpuBackend(Backend):
         """Diagnostic: device time (HIP events) of the last audit() or audit_select() query's
         kernels."""
         return self._diag_ms("raftsim_diag_audit_ms")
+
+    # -- cluster packs (include/raftsim.h, "Cluster packs") --------------------------------------
+    def gather_layout(self, parts=tuple(_abi.GATHER_PARTS)):
+        """Where the parts (names of _abi.GATHER_PARTS) stand in a cluster's record of this
+        handle: {"stride": bytes, part name: (offset, size)}."""
+        lay = _abi.GatherLayout()
+        mask = self._mask(parts, _abi.GATHER_PARTS, "pack part")
+        self._check(self._gather["layout"](self._h, mask, C.byref(lay)))
+        return lay.as_dict()
+
+    def gather(self, clusters, parts=tuple(_abi.GATHER_PARTS), limit=None):
+        """The full state of the given clusters as a ClusterPack, packed on the device and copied
+        once per device instead of once per node and part. `clusters` is a sequence of
+        handle-local cluster ids, or of the record dicts violations(), select() and
+        audit_select() return (their "cluster" key is used), in any order, duplicates allowed;
+        `limit` takes the first that many. `parts` names the parts to pack (_abi.GATHER_PARTS:
+        cluster, nodes, queues, logs, arenas, streams); nodes is always added, because the node
+        records carry the counts the other parts are read with. Stream-ordered: valid after
+        step_async, which it waits for. Read-only."""
+        ids = [int(c["cluster"] if isinstance(c, dict) else c) for c in clusters]
+        if limit is not None:
+            ids = ids[:int(limit)]
+        names = [k for k in _abi.GATHER_PARTS if k in set(parts) | {"nodes"}]
+        mask = self._mask(parts, _abi.GATHER_PARTS, "pack part") | _abi.GATHER_PARTS["nodes"]
+        lay = _abi.GatherLayout()
+        self._check(self._gather["layout"](self._h, mask, C.byref(lay)))
+        tick = self.tick
+        data = np.empty(len(ids) * int(lay.stride), dtype=np.uint8)
+        idx = np.asarray(ids, dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.C):
+            bad = next(i for i, c in enumerate(ids) if not 0 <= c < self.C)
+            raise ValueError(f"clusters[{bad}] = {ids[bad]} is outside the handle's {self.C}")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        got = self._check(int(self._gather["read"](
+            self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(ids), mask,
+            data.ctypes.data_as(C.c_void_p), data.size)))
+        assert got == data.size and list(lay.as_dict())[1:] == names
+        cfg = {f: getattr(self.config, f) for f, _ in _abi.Config._fields_}
+        return ClusterPack(cfg, tick, ids, lay.as_dict(), data)
+
+    def last_gather_ms(self):
+        """Diagnostic: device time (HIP events) of the last gather()'s kernels."""
+        return self._diag_ms("raftsim_diag_gather_ms")
 
     def replay_config(self, cluster, **overrides):
         """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster
