@@ -1,0 +1,317 @@
+"""The reference side of the high-clock tests, without a GPU (tests/high_clock.py has the bases).
+
+1. pyref steps a cluster at a tick given as a Python integer, so nothing in it wraps: the C oracle
+   moved to SIGN (across 2^31) and TOP (ending on the last tick a step may end at) equals it in
+   every node field, queue, log, cluster record, trace dump and counter.
+2. Witnesses: for every configuration of tests/test_gpu_high_clock.py, at every base, the oracle's
+   counters show a run that is far from trivial (floors of half the values measured on the CPU),
+   so the GPU comparisons cannot pass on idle clusters.
+3. The horizon on the oracle: a step may end exactly at last_end(cfg); one more tick is refused.
+"""
+import numpy as np
+import pytest
+
+import census_oracle
+import helpers
+import high_clock as hc
+import pyref
+import test_gpu_high_clock as gpu_cases
+
+TICKS = 600
+# 4 clusters, N = 5, with every fault, the bursty client and the trace rings
+BASE = dict(n_clusters=4, nodes=5, seed=0x123456789, hb=6, el_base=9, el_span=9, client_ppm=200000,
+            client_period=37, client_burst=11, client_redirects=3, log_cap=32, drop_ppm=100000,
+            dup_ppm=100000, dmin=1, dmax=5, part_ppm=300000, part_epoch=7, trace_cap=64,
+            trace_entry_cap=64)
+PY_CASES = {
+    "n2": dict(nodes=2), "n5": dict(), "n9": dict(nodes=9),
+    "n9_spec": dict(nodes=9, variant_flags=2),
+    "variant1": dict(variant_flags=1), "variant2": dict(variant_flags=2),
+    "variant3": dict(variant_flags=3),
+    "epoch_1": dict(part_epoch=1), "epoch_1000": dict(part_epoch=1000),
+    "epoch_65537": dict(part_epoch=65537), "epoch_2p31": dict(part_epoch=2 ** 31 + 3),
+    "period_0": dict(client_period=0, client_burst=0),
+    "period_4096": dict(client_period=4096, client_burst=1024),
+    "period_2p31": dict(client_period=2 ** 31 + 5, client_burst=2 ** 30 + 1),
+}
+
+
+@pytest.mark.parametrize("base", ["sign0", "top"])
+@pytest.mark.parametrize("name", list(PY_CASES))
+def test_python_integers_equal_the_oracle(name, base):
+    cfg = dict(BASE, **PY_CASES[name])
+    T0 = hc.base_tick(base, cfg, TICKS)
+    pcs = hc.start(hc.py_clusters, cfg, T0)
+    be = hc.start(helpers.oracle, cfg, T0)
+    t = T0
+    for n in (1, 7, TICKS - 8):
+        for pc in pcs:
+            for k in range(n):
+                pc.step(t + k)
+        be.step(n)
+        t += n
+        assert be.tick == t
+        assert be.counters()["payload_evicted"] == 0
+        for c, pc in enumerate(pcs):
+            helpers.compare_py_backend(pc, be, c)
+    c = be.counters()
+    for k in pyref.COUNTERS:
+        assert c[k] == sum(pc.cnt[k] for pc in pcs), (k, c[k])
+    assert c["payload_max"] == max(pc.payload_max for pc in pcs)
+    firsts = [pc.first_violation for pc in pcs if pc.first_violation is not None]
+    assert c["first_violation_tick"] == (min(firsts) if firsts else None)
+    # (the faithful model at N = 9 elects nobody under these faults: all nine time out together)
+    assert (c["leaders"] > 0 or name == "n9") and c["ev_timeout"] > 0 and c["delivered"] > 100
+    if base == "top":
+        hc.refused_at_the_end(be, cfg)
+    be.close()
+
+
+def test_first_on_tick():
+    for P, B in ((0, 0), (37, 11), (4096, 1024), (2 ** 31 + 5, 2 ** 30 + 1)):
+        for t in (0, 10, 11, 36, 37, 50_000, 2 ** 31 - 300, 2 ** 31 + 4, 2 ** 31 + 5,
+                  2 ** 32 - 700):
+            got = hc.first_on_tick(t, P, B)
+            want = next((u for u in range(t, t + 40) if P == 0 or u % P < B), None)
+            if want is None:                     # the next window is far: its first tick, or never
+                want = min((t // P + 1) * P, 2 ** 32 - 1)
+            assert got == want, (P, B, t)
+    assert hc.first_on_tick(2 ** 32 - 700, 2 ** 31 + 5, 2 ** 30 + 1) == 2 ** 32 - 1
+
+
+def test_bases():
+    cfg = dict(hb=40, el_base=60, el_span=60, dmax=10)
+    assert hc.longest(cfg) == 120 and hc.longest({}) == 10000
+    assert hc.longest(dict(hb=300, el_base=9, el_span=9, dmax=5)) == 300
+    assert hc.last_end(cfg) == 2 ** 32 - 122
+    assert hc.base_tick("sign0", cfg, 6000) + 3000 == 2 ** 31
+    assert hc.base_tick("sign7", cfg, 6000) + 3007 == 2 ** 31
+    assert hc.base_tick("top", cfg, 6000) + 6000 == hc.last_end(cfg)
+    assert hc.base_tick("low", cfg, 6000) == 50_000
+
+
+@pytest.mark.parametrize("cfg", [
+    dict(n_clusters=4, nodes=5, seed=1),
+    dict(BASE, hb=300),
+    dict(gpu_cases.GENERAL["clients_n5"], n_clusters=8),
+], ids=["default_timers", "hb_longest", "clients_n5"])
+def test_the_horizon(cfg):
+    """A step that ends exactly at last_end(cfg) is accepted; one more tick is refused with the
+    2^32 message, the digest is unchanged, and step(0) still works. So is a single step that
+    would end one tick later, from further away."""
+    be = hc.start(helpers.oracle, cfg, hc.TOP(cfg, 300))
+    be.step(100)
+    before = be.digest()
+    with pytest.raises(helpers.RaftSimError, match=r"2\^32"):
+        be.step(201)
+    assert be.tick == hc.last_end(cfg) - 200 and np.array_equal(be.digest(), before)
+    be.step(200)
+    hc.refused_at_the_end(be, cfg)
+    be.close()
+
+
+# -- witnesses ----------------------------------------------------------------------------------
+KEYS = ("leaders", "ev_timeout", "delivered", "overflow", "partitioned", "duplicated", "dropped",
+        "client_injected", "redirects", "entries_appended", "viol_election", "viol_log",
+        "viol_complete")
+WITNESSED = dict(gpu_cases.GENERAL, **gpu_cases.TRACED, **gpu_cases.QUERIES)
+# The counters KEYS of the oracle after the 6,000 ticks of each case, per base in the order of
+# high_clock.BASES, measured on the CPU (no figure here comes from a GPU). A counter the
+# configuration leaves off is 0. period_2p31 at TOP injects nothing: its next window starts past
+# the clock and the cursor saturates at "never".
+MEASURED = {
+    "faults_n5": ((3174, 21120, 202629, 0, 10763, 2054, 23924, 0, 0, 0, 122, 0, 0),
+                  (3153, 21095, 201850, 0, 10749, 2162, 23586, 0, 0, 0, 113, 0, 0),
+                  (2980, 21739, 199018, 0, 10818, 2090, 23437, 0, 0, 0, 108, 0, 0),
+                  (2951, 21848, 200237, 0, 10635, 2176, 23686, 0, 0, 0, 120, 0, 0)),
+    "clients_n5": ((1980, 21652, 170252, 0, 9127, 1755, 19981, 5632, 9731, 2244, 78, 416, 0),
+                   (2003, 21194, 162361, 0, 8830, 1752, 19287, 5502, 8616, 2502, 77, 465, 1),
+                   (2059, 20776, 163617, 0, 9036, 1822, 19319, 5502, 8513, 2728, 100, 527, 2),
+                   (1723, 20787, 149699, 0, 8196, 1561, 18207, 5502, 10429, 2636, 80, 498, 2)),
+    "n2": ((868, 11617, 40651, 0, 2185, 400, 4607, 995, 0, 652, 1, 21, 80),
+           (880, 11850, 40396, 0, 2542, 401, 4647, 995, 0, 496, 2, 19, 100),
+           (890, 11202, 41197, 0, 2460, 435, 4586, 995, 0, 478, 2, 19, 91),
+           (875, 11561, 41933, 0, 2263, 441, 4723, 995, 0, 406, 1, 18, 77)),
+    "n3": ((2098, 10670, 80549, 0, 4609, 949, 9750, 990, 0, 264, 17, 10, 0),
+           (2036, 10743, 79872, 0, 4761, 847, 9783, 990, 0, 388, 18, 14, 0),
+           (2012, 11210, 77068, 0, 4894, 859, 9576, 990, 0, 347, 16, 14, 0),
+           (2137, 11215, 78717, 0, 4875, 920, 9875, 990, 0, 246, 25, 6, 0)),
+    "n4": ((3167, 10973, 122882, 0, 8043, 1463, 15668, 940, 0, 176, 62, 4, 0),
+           (3131, 11075, 121550, 0, 7640, 1429, 15672, 940, 0, 137, 80, 1, 0),
+           (3251, 11258, 125243, 0, 7520, 1472, 15812, 940, 0, 161, 82, 2, 0),
+           (3416, 10906, 128925, 0, 7225, 1501, 16238, 940, 0, 148, 78, 2, 0)),
+    "n6": ((4353, 18102, 252724, 0, 13783, 2727, 30318, 1004, 0, 90, 167, 0, 0),
+           (4291, 18446, 253882, 0, 14606, 2666, 30518, 1004, 0, 82, 169, 3, 3),
+           (4467, 18449, 256187, 0, 14702, 2879, 30378, 1004, 0, 67, 175, 0, 0),
+           (4142, 18467, 249454, 0, 15382, 2782, 29707, 1004, 0, 85, 153, 0, 0)),
+    "n8": ((3934, 27400, 420144, 0, 21252, 4438, 48660, 962, 0, 37, 240, 0, 0),
+           (4056, 26510, 418483, 0, 21453, 4388, 47820, 962, 0, 49, 226, 0, 0),
+           (4085, 26922, 423462, 0, 21431, 4494, 48712, 962, 0, 41, 237, 0, 0),
+           (3873, 27229, 417787, 0, 21061, 4222, 48532, 962, 0, 40, 213, 0, 0)),
+    "burst_n7": ((17, 4543, 709072, 0, 1950, 422, 4837, 133785, 530746, 11903, 0, 30, 0),
+                 (12, 4591, 700837, 0, 1899, 480, 4907, 131204, 524816, 0, 0, 0, 0),
+                 (16, 4587, 699612, 0, 1864, 485, 4843, 131204, 523172, 3676, 1, 6, 0),
+                 (17, 4571, 694622, 0, 2012, 435, 4809, 131204, 518534, 14920, 0, 34, 0)),
+    "burst_n9": ((6, 5311, 733794, 0, 3037, 630, 7480, 133250, 531884, 5264, 0, 33, 0),
+                 (8, 5368, 723043, 0, 2730, 708, 7858, 130661, 522644, 0, 0, 0, 0),
+                 (6, 5314, 720777, 0, 2776, 675, 7634, 130661, 520970, 5373, 0, 19, 0),
+                 (7, 5286, 723013, 0, 2318, 747, 7582, 130661, 522644, 0, 2, 0, 0)),
+    "burst_n8_inbox2": ((6, 4957, 676265, 21635, 2425, 503, 5289, 133555, 515517, 5820, 0, 32, 0),
+                        (1, 4987, 664996, 21736, 2360, 462, 5272, 130924, 506761, 0, 0, 0, 0),
+                        (5, 4967, 663532, 21603, 2365, 489, 5258, 130924, 505238, 7111, 0, 30, 0),
+                        (5, 4967, 664374, 21575, 2423, 525, 5423, 130924, 506205, 0, 0, 0, 0)),
+    "burst_n7_short": (
+        (1535, 24855, 728064, 785, 14707, 2929, 31173, 133785, 337979, 180974, 77, 1116, 0),
+        (1408, 24733, 731334, 188, 13301, 2782, 30937, 131204, 343571, 192593, 65, 1061, 0),
+        (1625, 24037, 697712, 237, 13218, 2828, 30344, 131204, 317487, 200498, 68, 1511, 0),
+        (1360, 24448, 763062, 182, 12243, 2644, 30337, 131204, 383065, 134973, 61, 559, 0)),
+    "burst_n9_short": (
+        (906, 30947, 964458, 470, 20966, 4155, 46869, 133250, 427855, 64065, 53, 976, 0),
+        (1014, 31049, 970208, 208, 21231, 4317, 47122, 130661, 429006, 61513, 61, 803, 0),
+        (1209, 30347, 944480, 88, 20864, 4159, 46639, 130661, 412521, 65638, 72, 833, 0),
+        (1056, 30175, 1005930, 0, 17036, 4154, 46817, 130661, 464396, 40095, 71, 673, 0)),
+    "spec_n5": ((4696, 8665, 312676, 0, 13559, 3067, 34060, 3174, 0, 2886, 0, 0, 0),
+                (4628, 8554, 311390, 0, 15100, 3077, 33845, 3174, 0, 3054, 0, 0, 0),
+                (4836, 8830, 312684, 0, 15393, 3074, 34374, 3174, 0, 2890, 0, 0, 0),
+                (4641, 8380, 313512, 0, 12949, 3118, 33715, 3174, 0, 3191, 0, 0, 0)),
+    "spec_n8": ((6733, 13244, 594398, 0, 21310, 5813, 64916, 3171, 0, 2601, 0, 0, 0),
+                (6613, 14030, 590952, 0, 26372, 5825, 64373, 3171, 0, 2996, 0, 0, 0),
+                (6555, 14054, 590350, 0, 26890, 5891, 64922, 3171, 0, 2802, 0, 0, 0),
+                (6611, 13939, 590716, 0, 24942, 5847, 65249, 3171, 0, 2674, 0, 0, 0)),
+    "variant1_n5": ((1225, 14612, 129038, 0, 8724, 1656, 18272, 29040, 0, 5767, 40, 655, 45),
+                    (1242, 14518, 131993, 0, 7672, 1701, 18522, 29040, 0, 6001, 32, 719, 38),
+                    (1253, 14277, 129619, 0, 7719, 1674, 18366, 29040, 0, 5883, 28, 631, 49),
+                    (1211, 15077, 133060, 0, 8371, 1656, 18414, 29040, 0, 5470, 36, 577, 41)),
+    "spec_nolog_n5": ((4679, 8218, 338339, 0, 13945, 3046, 34304, 29049, 0, 25659, 0, 0, 1051),
+                      (4637, 8277, 337891, 0, 14347, 3058, 33478, 29049, 0, 25803, 0, 0, 1157),
+                      (4628, 8209, 338027, 0, 14456, 3089, 33515, 29049, 0, 25342, 0, 0, 1060),
+                      (4656, 8167, 338314, 0, 13698, 3005, 33683, 29049, 0, 25878, 0, 0, 1038)),
+    # (N = 9 with two-slot inboxes elects almost nobody, as the `overflow` shape does from tick 0)
+    "overflow": ((0, 28786, 367186, 286560, 0, 148961, 0, 7450, 0, 0, 0, 0, 0),
+                 (2, 28679, 366648, 286950, 0, 149510, 0, 7450, 0, 1, 0, 0, 0),
+                 (3, 28666, 367015, 287239, 0, 149335, 0, 7450, 0, 3, 0, 0, 0),
+                 (2, 28622, 366361, 285803, 0, 148668, 0, 7450, 0, 191, 0, 7, 0)),
+    "arena_odd": ((669, 12508, 137614, 0, 0, 15235, 0, 28969, 0, 9557, 5, 2133, 8),
+                  (625, 12901, 141257, 0, 0, 15518, 0, 28969, 0, 10037, 0, 2321, 2),
+                  (676, 11777, 138513, 0, 0, 15588, 0, 28969, 0, 10700, 3, 2321, 6),
+                  (602, 12147, 136596, 0, 0, 15217, 0, 28969, 0, 11159, 2, 2652, 4)),
+    "tiny_launches": ((2082, 21589, 172033, 0, 9369, 1752, 19712, 5423, 9138, 2305, 82, 466, 0),
+                      (1985, 21406, 168159, 0, 8785, 1846, 19803, 5317, 9201, 2472, 87, 495, 0),
+                      (2068, 20722, 161906, 0, 9063, 1732, 19401, 5317, 7700, 2730, 99, 539, 1),
+                      (1588, 21461, 147671, 0, 8079, 1609, 17790, 5317, 9298, 2687, 71, 543, 0)),
+    "epoch_1": ((2770, 22183, 197340, 0, 12316, 2089, 23426, 0, 0, 0, 115, 0, 0),
+                (2746, 21936, 193944, 0, 12350, 2086, 23151, 0, 0, 0, 116, 0, 0),
+                (2863, 21965, 195915, 0, 12262, 2114, 23018, 0, 0, 0, 104, 0, 0),
+                (2702, 22141, 195157, 0, 11890, 2086, 22980, 0, 0, 0, 91, 0, 0)),
+    "epoch_3": ((2962, 21683, 196998, 0, 11644, 2117, 23071, 0, 0, 0, 91, 0, 0),
+                (2898, 21528, 196035, 0, 11715, 2043, 23277, 0, 0, 0, 119, 0, 0),
+                (2741, 22620, 199637, 0, 11828, 2156, 23254, 0, 0, 0, 101, 0, 0),
+                (3064, 21246, 200606, 0, 11766, 2101, 23537, 0, 0, 0, 124, 0, 0)),
+    "epoch_1000": ((3234, 19640, 206472, 0, 11245, 2071, 24355, 0, 0, 0, 91, 0, 0),
+                   (3468, 18212, 210132, 0, 9375, 2214, 24394, 0, 0, 0, 76, 0, 0),
+                   (3341, 18874, 207903, 0, 9378, 2147, 24264, 0, 0, 0, 81, 0, 0),
+                   (3285, 19417, 208609, 0, 12426, 2182, 24165, 0, 0, 0, 96, 0, 0)),
+    "epoch_65537": ((3446, 18472, 209182, 0, 6992, 2100, 24486, 0, 0, 0, 93, 0, 0),
+                    (3444, 18721, 208741, 0, 9906, 2238, 24323, 0, 0, 0, 77, 0, 0),
+                    (3358, 19198, 207175, 0, 9869, 2163, 24248, 0, 0, 0, 78, 0, 0),
+                    (3477, 18472, 211721, 0, 7492, 2205, 24273, 0, 0, 0, 110, 0, 0)),
+    "epoch_2p31": ((3446, 18472, 209182, 0, 6992, 2100, 24486, 0, 0, 0, 93, 0, 0),
+                   (3440, 18289, 209397, 0, 9020, 2234, 24417, 0, 0, 0, 72, 0, 0),
+                   (3437, 18483, 209418, 0, 9196, 2148, 24419, 0, 0, 0, 80, 0, 0),
+                   (3373, 19161, 208311, 0, 10340, 2180, 24102, 0, 0, 0, 102, 0, 0)),
+    "period_37": ((867, 21518, 128319, 0, 7254, 1354, 15373, 8888, 15645, 1949, 35, 347, 3),
+                  (860, 21280, 125850, 0, 7320, 1385, 15239, 8876, 14760, 2328, 25, 447, 4),
+                  (857, 20953, 123408, 0, 7237, 1387, 14955, 8888, 14526, 2209, 34, 446, 4),
+                  (923, 20803, 124515, 0, 7123, 1348, 15226, 8859, 14401, 2194, 26, 382, 4)),
+    "period_2p31": ((619, 17735, 150493, 0, 6015, 1145, 12496, 29360, 53118, 4306, 29, 850, 5),
+                    (1885, 20098, 168542, 0, 8357, 1696, 18418, 15787, 19007, 3148, 79, 558, 0),
+                    (1916, 19865, 169159, 0, 8448, 1737, 18461, 15751, 18903, 3576, 89, 660, 3),
+                    (2880, 21936, 197393, 0, 10574, 2115, 23512, 0, 0, 0, 140, 0, 0)),
+    "lite_n6": ((257, 5621, 331340) + (0,) * 10, (258, 5754, 330760) + (0,) * 10,
+                (256, 5271, 333230) + (0,) * 10, (256, 5306, 332770) + (0,) * 10),
+    "lite_n7_d4": ((242, 13144, 369528) + (0,) * 10, (243, 13198, 370008) + (0,) * 10,
+                   (245, 13575, 369367) + (0,) * 10, (236, 13840, 368814) + (0,) * 10),
+    "lite_n9_inbox4": ((2, 26696, 310430, 108970) + (0,) * 9, (5, 26483, 309729, 108831) + (0,) * 9,
+                       (1, 26738, 311026, 109006) + (0,) * 9, (1, 26691, 309891, 108797) + (0,) * 9),
+    "lite_n9": ((167, 17968, 467136) + (0,) * 10, (171, 17650, 467544) + (0,) * 10,
+                (185, 17162, 470848) + (0,) * 10, (178, 17226, 468880) + (0,) * 10),
+    "spec_lite_n6_elections": ((22110, 30537, 547125) + (0,) * 10, (22074, 30301, 545391) + (0,) * 10,
+                               (22085, 30196, 544574) + (0,) * 10, (22069, 30188, 544242) + (0,) * 10),
+    "traced_n5": ((2277, 20270, 170844, 0, 9507, 1883, 20411, 3103, 0, 326, 55, 14, 0),
+                  (2375, 20001, 170241, 0, 9620, 1823, 20625, 3103, 0, 279, 45, 11, 1),
+                  (2250, 20528, 168402, 0, 9815, 1855, 20523, 3103, 0, 314, 58, 17, 0),
+                  (2315, 20086, 168083, 0, 10641, 1806, 20415, 3103, 0, 243, 50, 11, 1)),
+    "traced_n6": ((257, 5681, 323310) + (0,) * 10, (256, 5709, 323210) + (0,) * 10,
+                  (258, 5471, 324015) + (0,) * 10, (260, 5738, 323365) + (0,) * 10),
+    "spec_nolog_n5_512": (
+        (9356, 16632, 671039, 0, 29707, 6041, 68372, 54104, 0, 48188, 0, 0, 1938),
+        (9383, 16443, 672857, 0, 28462, 6090, 67512, 54104, 0, 48603, 0, 0, 2137),
+        (9410, 16567, 673468, 0, 28456, 6198, 67689, 54104, 0, 47269, 0, 0, 2049),
+        (9394, 16779, 671127, 0, 29607, 5995, 67512, 54104, 0, 48479, 0, 0, 1987)),
+}
+# the schedule changes no result: the packing alone
+MEASURED["sched_aligned"] = MEASURED["sched_fixed"] = MEASURED["clients_n5"]
+# LITE plans (test_gpu_high_clock.lite_cfg): (leaders, ev_timeout, delivered, clusters with
+# exactly one live leader at the end) per base
+LITE_MEASURED = {
+    (2, 1): ((256, 3939, 671458, 256), (256, 3827, 671861, 256), (256, 3749, 672129, 256),
+             (256, 3917, 671525, 256)),
+    (2, 3): ((256, 3912, 671183, 256), (256, 3987, 670816, 256), (256, 3884, 671291, 256),
+             (256, 4006, 670796, 256)),
+    (3, 1): ((257, 2841, 1358980, 256), (257, 2915, 1358166, 256), (256, 2902, 1358400, 256),
+             (259, 2926, 1358270, 256)),
+    (3, 3): ((256, 2937, 1358536, 256), (257, 3018, 1357964, 256), (259, 3000, 1357974, 256),
+             (257, 2855, 1359132, 256)),
+    (4, 1): ((256, 2968, 2043411, 256), (256, 3038, 2042973, 256), (258, 3049, 2042805, 256),
+             (256, 3024, 2042763, 256)),
+    (4, 3): ((261, 3055, 2044035, 256), (258, 3054, 2044557, 256), (261, 3046, 2044392, 256),
+             (258, 3107, 2043612, 256)),
+    (5, 1): ((258, 6383, 2687132, 256), (256, 6321, 2688096, 256), (257, 6459, 2686012, 256),
+             (256, 6237, 2689484, 256)),
+    (5, 3): ((259, 6565, 2690816, 256), (257, 6307, 2693844, 256), (258, 6645, 2690372, 256),
+             (261, 6756, 2688176, 256)),
+}
+# the fault-free N >= 6 cases that must settle: at least half of the clusters end with exactly one
+# live leader (measured: lite_n6 256, lite_n7_d4 233, lite_n9 166 at the least, spec_lite 235).
+# lite_n9_inbox4 is not among them: nine timers that fire together overflow four-slot inboxes for
+# good and at most 5 clusters ever elect; it runs elections and overflows throughout instead.
+LITE_N6 = ("lite_n6", "lite_n7_d4", "lite_n9", "spec_lite_n6_elections")
+
+
+def witness_run(cfg, base, chunks):
+    T0 = hc.base_tick(base, cfg, sum(chunks))
+    r = hc.start(gpu_cases.oracle, cfg, T0)
+    for n in chunks:
+        r.step(n)
+    c = r.counters()
+    one = census_oracle.of_backend(r)[0]["by_class"]["one_leader"]
+    r.close()
+    return c, one
+
+
+@pytest.mark.parametrize("name", list(WITNESSED))
+def test_general_cases_are_not_trivial(name):
+    cfg = WITNESSED[name]
+    for base, measured in zip(hc.BASES, MEASURED[name]):
+        c, one = witness_run(cfg, base, gpu_cases.CHUNKS)
+        print(name, base, tuple(c[k] for k in KEYS), one)
+        for k, m in zip(KEYS, measured):
+            assert c[k] >= m // 2, (base, k, c[k], m)
+        assert c["leaders"] > 0 or name == "overflow", base
+        assert c["ev_timeout"] >= cfg["n_clusters"] and c["delivered"] > 0
+        if name in LITE_N6:
+            assert 2 * one >= cfg["n_clusters"], (base, one)
+        if name in gpu_cases.QUERIES:
+            assert c["viol_election"] + c["viol_log"] + c["viol_complete"] >= 16, base
+
+
+@pytest.mark.parametrize("nodes,d", gpu_cases.LITE)
+def test_lite_plans_settle(nodes, d):
+    cfg, P, plan = gpu_cases.lite_cfg(nodes, d)
+    for base, measured in zip(hc.BASES, LITE_MEASURED[nodes, d]):
+        c, one = witness_run(cfg, base, plan)
+        got = (c["leaders"], c["ev_timeout"], c["delivered"], one)
+        print(nodes, d, base, got)
+        for x, m in zip(got, measured):
+            assert x >= m // 2, (base, got, measured)
+        assert 2 * one >= cfg["n_clusters"], (base, one)

@@ -148,3 +148,31 @@ def test_one_cluster_handles_sum_to_the_whole_handle():
     assert all(0 <= c < 96 and any(counts) for c, (_, counts) in exp.items())
     recs = viol_oracle.as_records(exp)
     assert [r["cluster"] for r in recs] == sorted(exp) and len(recs) == len(exp)
+
+
+def test_one_cluster_handles_sum_to_the_whole_handle_across_2_31():
+    """The same method from a moved clock (expected_records' tick0 and setup): the whole handle
+    and the one-cluster handles are moved to 2^31 - 3000 and given their client cursors as
+    high_clock.start does; the sums and the earliest first tick agree at three checkpoints, the
+    last two at and above 2^31. (Measured at 96 clusters: election 18 / log 295 / complete 11 at
+    the end, first tick 2147481308.)"""
+    import high_clock as hc
+    from test_gpu_high_clock import GENERAL
+
+    cfg = dict(GENERAL["variant1_n5"], n_clusters=96)
+    T0 = hc.SIGN(6000)
+    points = (T0 + 1500, T0 + 3000, T0 + 6000)
+    per_step = viol_oracle.expected_records(cfg, 96, points, tick0=T0, setup=hc.setup_for(cfg, T0))
+    whole = hc.start(helpers.oracle, cfg, T0)
+    assert points[1] == 2 ** 31
+    for t, exp in zip(points, per_step):
+        whole.step(t - whole.tick)
+        c = whole.counters()
+        print(t, {k: c["viol_" + k] for k in viol_oracle.KINDS}, c["first_violation_tick"])
+        for i, k in enumerate(viol_oracle.KINDS):
+            assert sum(counts[i] for _, counts in exp.values()) == c["viol_" + k], (t, k)
+        assert min(first for first, _ in exp.values()) == c["first_violation_tick"], t
+        assert all(T0 <= first < t for first, _ in exp.values())
+    for i, k in enumerate(viol_oracle.KINDS):
+        assert sum(1 for _, counts in per_step[-1].values() if counts[i]) >= 1, k
+    assert any(first >= 2 ** 31 for first, _ in per_step[-1].values())

@@ -18,10 +18,18 @@ def _key(cfg, n_clusters):
     return tuple(sorted(cfg.items())), n_clusters
 
 
-def _handles(cfg, n_clusters):
+def _handles(cfg, n_clusters, tick0=0, setup=None):
+    """One-cluster handles of the first n_clusters clusters of cfg; with tick0 each is moved there
+    by set_tick, then given to setup(handle) (it writes the client cursor: high_clock.setup_for),
+    as high_clock.start moves the whole handle."""
     off = cfg.get("cluster_offset", 0)
-    return [helpers.oracle(**dict(cfg, n_clusters=1, cluster_offset=off + c, n_devices=1))
-            for c in range(n_clusters)]
+    for c in range(n_clusters):
+        h = helpers.oracle(**dict(cfg, n_clusters=1, cluster_offset=off + c, n_devices=1))
+        if tick0:
+            h.set_tick(tick0)
+        if setup is not None:
+            setup(h)
+        yield h
 
 
 def _counts(h):
@@ -29,15 +37,16 @@ def _counts(h):
     return tuple(c["viol_" + k] for k in KINDS), c["first_violation_tick"]
 
 
-def expected_records(cfg, n_clusters, ticks):
-    """{cluster: (first_tick, (election, log, complete))} of the clusters with any violation after
-    `ticks` ticks of the first n_clusters clusters of cfg. `ticks` may be a tuple of increasing
-    checkpoints: then a list with one such dict per checkpoint. Computed once per argument set."""
+def expected_records(cfg, n_clusters, ticks, tick0=0, setup=None):
+    """{cluster: (first_tick, (election, log, complete))} of the clusters with any violation at
+    tick `ticks` of the first n_clusters clusters of cfg. `ticks` may be a tuple of increasing
+    checkpoints: then a list with one such dict per checkpoint. With tick0 the run starts there
+    (see _handles) and the checkpoints are absolute ticks. Computed once per argument set."""
     points = (ticks,) if isinstance(ticks, int) else tuple(ticks)
-    key = _key(cfg, n_clusters) + (points,)
+    key = _key(cfg, n_clusters) + (points, tick0, setup is not None)
     if key not in _cache:
         out = [dict() for _ in points]
-        for c, h in enumerate(_handles(cfg, n_clusters)):
+        for c, h in enumerate(_handles(cfg, n_clusters, tick0, setup)):
             for i, t in enumerate(points):
                 h.step(t - h.tick)
                 counts, first = _counts(h)
@@ -49,16 +58,17 @@ def expected_records(cfg, n_clusters, ticks):
     return res[0] if isinstance(ticks, int) else res
 
 
-def expected_window(cfg, n_clusters, t0, t1, step=100):
+def expected_window(cfg, n_clusters, t0, t1, step=100, tick0=0, setup=None):
     """The records of the violations counted in ticks [t0, t1) alone (what a handle whose records
     were cleared at t0 holds at t1): {cluster: ((lo, hi), counts)}, counts the one-cluster
     handle's counter delta over [t0, t1) and [lo, hi) the `step`-tick stretch in which its
-    counters first moved after t0 (the first violation tick of the window lies in it)."""
-    key = _key(cfg, n_clusters) + ("window", t0, t1, step)
+    counters first moved after t0 (the first violation tick of the window lies in it). With tick0
+    the run starts there (see _handles); t0 and t1 are absolute ticks."""
+    key = _key(cfg, n_clusters) + ("window", t0, t1, step, tick0, setup is not None)
     if key not in _cache:
         out = {}
-        for c, h in enumerate(_handles(cfg, n_clusters)):
-            h.step(t0)
+        for c, h in enumerate(_handles(cfg, n_clusters, tick0, setup)):
+            h.step(t0 - h.tick)
             base, _ = _counts(h)
             span = None
             while h.tick < t1:
