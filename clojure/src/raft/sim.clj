@@ -321,6 +321,24 @@
       (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
       {:layout layout :buffer m})))
 
+(defn scatter
+  "The way back (raft_scatter_write): record (nth rs i) of `buffer`, a Memory of n-records records
+  of `parts` as gather returns it, becomes cluster (nth cs i) of sim; rs nil takes record i. A
+  record may be named any number of times (one state, many futures), a cluster once. `parts` must
+  hold :cluster :nodes :queues :arenas, and :streams when the handle keeps commit streams. Does not
+  set the clock (set-tick!). Returns the number of clusters written."
+  [sim cs rs parts buffer n-records]
+  (let [n (count cs)
+        ints (fn [xs] (let [m (Memory. (* 4 (max 1 n)))]
+                        (doseq [[i x] (map-indexed vector xs)] (.setInt m (* 4 i) (unchecked-int x)))
+                        m))
+        mask (int (reduce bit-or 0 (map gather-parts parts)))
+        rc (.invokeLong (f "raft_scatter_write")
+                        (object-array [(:ptr sim) (ints cs) (when rs (ints rs)) (int n) mask buffer
+                                       (int n-records)]))]
+    (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
+    rc))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "scatter_host.hpp"
 #include "summary_host.hpp"
 
 namespace rs {
@@ -40,6 +41,9 @@ hipError_t launch_audit_select(uint32_t C, uint32_t any, uint32_t all, uint32_t 
 // gather_kernel.hip
 hipError_t launch_gather(const DevSim& S, const void* pairs, uint32_t n,
                          const raft_gather_layout_t& Y, void* out, hipStream_t st);
+// scatter_kernel.hip
+hipError_t launch_scatter(const DevSim& S, const void* pairs, uint32_t n,
+                          const raft_gather_layout_t& Y, const void* in, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -143,6 +147,9 @@ struct Shard {
   size_t gscratch_bytes;
   std::vector<hipEvent_t> gev;
   double gather_ms;
+  // raft_scatter_write (scatter_kernel.hip) uploads its records and lists into the same scratch and
+  // times its chunks' kernels with the same events (raftsim_diag_scatter_ms).
+  double scatter_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
 // The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
@@ -597,20 +604,11 @@ static int sh_write_nodes(Shard* s, uint32_t c0, uint32_t nc, const raft_node_t*
   s->audit_valid = false;
   if (!in) return fail(-EINVAL, "null input");
   HIP_OK(hipSetDevice(s->cfg.device));
-  const uint32_t N = s->N, all = ((1u << (N + 1)) - 1) & ~1u;
+  const uint32_t N = s->N;
   const size_t n0 = (size_t)c0 * N, cnt = (size_t)nc * N;
-  for (size_t i = 0; i < cnt; ++i) {
-    const raft_node_t* n = &in[i];
-    uint32_t id = (uint32_t)(i % N) + 1, peers = all & ~(1u << id);
-    if (n->role > 3 || n->voted_for > N || n->leader_id > N || n->fault > 4 ||
-        (n->votes & ~all) || (n->ls_keys & ~peers) || n->entries_is_seq > 1 ||
-        n->ls_present > 1 || n->log_len > s->L ||
-        n->arena_frontier - n->arena_base < n->log_len ||
-        n->arena_frontier - n->arena_base > s->L ||
-        (n->role == RAFT_LEADER && (!n->ls_present || n->ls_keys != peers)) ||
-        (!n->ls_present && n->ls_keys))
+  for (size_t i = 0; i < cnt; ++i)
+    if (!rs::node_record_ok(in[i], (uint32_t)(i % N) + 1, N, s->L))
       return fail(-EINVAL, "invalid node record");
-  }
   // the queue words of the blocks (qmeta, head/tail arrivals) and the cluster words are kept
   const size_t HB = s->d.HB;
   std::vector<uint32_t> blk(nc * HB), ccv(cnt);
@@ -666,17 +664,13 @@ static int sh_write_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t whic
   int rc = check_node(s, cluster, id);
   if (!rc) s->storm_until = 0;
   if (rc) return rc;
-  if (which > 1 || count > s->Q || (count && !in)) return fail(-EINVAL, "bad queue or count");
-  for (uint32_t i = 0; i < count; ++i) {
-    uint32_t type = in[i].hdr & 7, src = (in[i].hdr >> 3) & 15;
-    int want = type <= RAFT_MSG_CLIENT_SET ? 0 : 1;
-    if (type < 1 || type > 5 || want != (int)which || src > s->N || src == id ||
-        (type == RAFT_MSG_CLIENT_SET) != (src == 0) ||
-        (i > 0 && in[i].arrival < in[i - 1].arrival))
-      return fail(-EINVAL, "invalid message or order");
+  switch (rs::queue_fault(in, count, which, id, s->N, s->Q)) {
+    case rs::QUEUE_OK: break;
+    case rs::QUEUE_COUNT: return fail(-EINVAL, "bad queue or count");
+    default: return fail(-EINVAL, "invalid message or order");
   }
-  for (uint32_t i = 0; i < count; ++i)   // a queued client-set needs the general kernel (LITE)
-    if ((in[i].hdr & 7) == RAFT_MSG_CLIENT_SET) s->d.lite = 0;
+  // a queued client-set needs the general kernel (LITE)
+  if (rs::queue_has_client_set(in, count)) s->d.lite = 0;
   HIP_OK(hipSetDevice(s->cfg.device));
   const uint32_t gi = cluster * s->N + id - 1;
   std::vector<raft_msg_t> slots(s->Q);
@@ -1573,6 +1567,201 @@ int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, ui
 // in ms.
 extern "C" int raftsim_diag_gather_ms(raft_sim_t* r, double* ms) {
   return diag_ms(r, ms, &Shard::gather_ms);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cluster packs written back: the gather turned round. Everything that can refuse the call is
+// checked on the host first (scatter_host.hpp: the ranges, a target named twice, every referenced
+// record against the predicates of raft_sim_write_nodes and raft_sim_write_queue), so a refused
+// call has touched no device. The (record, target) pairs are sorted by owner shard and record and
+// cut into chunks of the shard's scratch (the gather's, GATHER_SCRATCH_BYTES): a chunk's distinct
+// records are uploaded once each, its (local cluster, slot) list behind them, and one kernel
+// writes its targets; the chunks of a shard follow each other on its stream, all shards run at
+// once, and every started shard is waited for. The host's bookkeeping of a touched shard is what
+// the per-node writes leave, taken together.
+static const char* const NODE_FAULT_TEXT[] = {
+    "", "role > 3", "voted_for > nodes", "leader_id > nodes", "fault > 4",
+    "votes outside ids 1..nodes", "ls_keys outside the peers", "entries_is_seq > 1", "ls_present > 1", "log_len > log_cap",
+    "arena_frontier - arena_base < log_len", "arena_frontier - arena_base > log_cap",
+    "a leader without its leader-state keys", "ls_keys without ls_present"};
+static const char* const QUEUE_FAULT_TEXT[] = {
+    "", "count > inbox_cap", "type outside 1..5", "a message of the other queue", "src > nodes",
+    "src is the node itself", "client-set and src 0 do not go together", "arrivals decrease"};
+
+int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32_t* records,
+                           uint32_t n, uint32_t parts, const void* in, uint32_t n_records) {
+  if (!r) return fail(-EINVAL, "null sim");
+  int rc = gather_parts_ok(parts);
+  if (rc) return rc;
+  static const char* const part_name[] = {"CLUSTER", "NODES",  "QUEUES",
+                                          "LOGS",    "ARENAS", "STREAMS"};
+  for (int b : {0, 1, 2, 4})
+    if (!((parts >> b) & 1))
+      return fail(-EINVAL, "raft_scatter_write needs the part RAFT_GATHER_%s", part_name[b]);
+  if (n && !clusters) return fail(-EINVAL, "null cluster list");
+  if (n && !in) return fail(-EINVAL, "null input");
+  if (r->cfg.commit_stream_cap && !(parts & RAFT_GATHER_STREAMS))
+    return fail(-EINVAL, "raft_scatter_write needs the part RAFT_GATHER_%s", part_name[5]);
+  char what[160];
+  for (uint32_t i = 0; i < n; ++i) {
+    if (clusters[i] >= r->cfg.n_clusters) {
+      snprintf(what, sizeof what, "clusters[%u] = %u is outside the handle's %u clusters", i,
+               clusters[i], r->cfg.n_clusters);
+      return fail(-EINVAL, "%s", what);
+    }
+    const uint32_t rec = records ? records[i] : i;
+    if (rec >= n_records) {
+      snprintf(what, sizeof what, "records[%u] = %u is outside the buffer's %u records", i, rec,
+               n_records);
+      return fail(-EINVAL, "%s", what);
+    }
+  }
+  const uint32_t dup = rs::first_duplicate(clusters, n);
+  if (dup < n) {
+    snprintf(what, sizeof what, "clusters[%u] = %u is a target twice", dup, clusters[dup]);
+    return fail(-EINVAL, "%s", what);
+  }
+  if (r->poisoned) return unusable();
+  if (!n) return 0;
+
+  raft_gather_layout_t Y;
+  gather_layout_of(r->sh[0], parts, &Y);
+  const uint64_t stride = Y.stride;
+  const size_t G = r->sh.size();
+  const rs::ScatterPlan plan = rs::scatter_plan(clusters, records, n, r->lo.data(), (uint32_t)G,
+                                                stride, GATHER_SCRATCH_BYTES);
+  const uint8_t* const src = static_cast<const uint8_t*>(in);
+  // every referenced record, once per chunk that uploads it; the first offending position is named
+  const rs::RecordShape shape = {r->cfg.nodes, r->cfg.inbox_cap, r->cfg.log_cap, Y.off[0], Y.off[1],
+                                 Y.off[2]};
+  std::vector<uint8_t> general(G, 0);
+  uint32_t bad_pos = UINT32_MAX;
+  rs::RecordVerdict bad = {};
+  for (const rs::ScatterChunk& ch : plan.chunks) {
+    size_t pi = ch.pair0;
+    for (size_t k = 0; k < ch.records; ++k) {
+      const rs::RecordVerdict v =
+          rs::record_verdict(src + (size_t)plan.records[ch.rec0 + k] * stride, shape);
+      general[ch.shard] |= v.general;
+      uint32_t pos = UINT32_MAX;                 // the record's first position in this chunk
+      for (; pi < ch.pair0 + ch.pairs && plan.pairs[pi].slot == k; ++pi)
+        pos = std::min(pos, plan.pos[pi]);
+      if (!v.ok() && pos < bad_pos) {
+        bad_pos = pos;
+        bad = v;
+      }
+    }
+  }
+  if (bad_pos != UINT32_MAX) {
+    const uint32_t rec = records ? records[bad_pos] : bad_pos;
+    if (bad.node_fault)
+      snprintf(what, sizeof what, "records[%u] = %u: invalid node record (node %u: %s)", bad_pos,
+               rec, bad.id, NODE_FAULT_TEXT[bad.node_fault]);
+    else
+      snprintf(what, sizeof what, "records[%u] = %u: invalid message or order (node %u, %s message "
+               "%u: %s)", bad_pos, rec, bad.id, bad.which ? "res" : "req", bad.msg,
+               QUEUE_FAULT_TEXT[bad.queue_fault]);
+    return fail(-EINVAL, "%s", what);
+  }
+
+  auto step = [&](hipError_t e) {
+    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_scatter_write: %s",
+                                          hipGetErrorString(e));
+    return !rc;
+  };
+  // Per shard: its chunks [first, first + count) of the plan and the scratch the largest needs. A
+  // chunk's records are staged in slot order (one host copy), unless they stand in the caller's
+  // buffer as a run in that order (a pack used whole: uploaded straight from the buffer).
+  std::vector<size_t> first(G, 0), count(G, 0);
+  for (size_t i = 0; i < plan.chunks.size(); ++i) {
+    const uint32_t d = plan.chunks[i].shard;
+    if (!count[d]) first[d] = i;
+    ++count[d];
+  }
+  // the staging buffers live until every shard has been waited for
+  std::vector<std::vector<uint8_t>> stages(plan.chunks.size());
+  std::vector<size_t> started;
+  for (size_t d = 0; d < G && !rc; ++d) {
+    if (!count[d]) continue;
+    Shard* s = r->sh[d];
+    started.push_back(d);
+    if (!step(hipSetDevice(s->cfg.device))) break;
+    // the bookkeeping of the per-node writes
+    s->storm_until = 0;
+    s->audit_valid = false;
+    s->keys_written = false;
+    if (general[d]) s->d.lite = 0;
+    size_t need = 0;
+    for (size_t i = first[d]; i < first[d] + count[d]; ++i)
+      need = std::max<size_t>(need, plan.chunks[i].bytes(stride));
+    if (s->gscratch_bytes < need) {
+      if (!step(hipStreamSynchronize(s->stream))) break;
+      if (s->gscratch) (void)hipFree(s->gscratch);
+      s->gscratch = nullptr;
+      s->gscratch_bytes = 0;
+      void* v = nullptr;
+      const hipError_t e = hipMalloc(&v, need);
+      if (e != hipSuccess) {
+        rc = fail(-ENOMEM, "hipMalloc failed in raft_scatter_write: %s", hipGetErrorString(e));
+        break;
+      }
+      s->gscratch = static_cast<uint8_t*>(v);
+      s->gscratch_bytes = need;
+    }
+    while (!rc && s->gev.size() < 2 * count[d]) {
+      hipEvent_t e;
+      if (step(hipEventCreate(&e))) s->gev.push_back(e);
+    }
+    for (size_t i = 0; i < count[d] && !rc; ++i) {
+      const rs::ScatterChunk& ch = plan.chunks[first[d] + i];
+      const uint32_t* const recs = plan.records.data() + ch.rec0;
+      bool run = true;                           // the records stand in the buffer as in the chunk
+      for (size_t k = 1; k < ch.records && run; ++k) run = recs[k] == recs[0] + k;
+      const uint8_t* up = src + (size_t)recs[0] * stride;
+      if (!run) {
+        std::vector<uint8_t>& st = stages[first[d] + i];
+        st.resize(ch.records * stride);
+        for (size_t k = 0; k < ch.records; ++k)
+          memcpy(st.data() + k * stride, src + (size_t)recs[k] * stride, stride);
+        up = st.data();
+      }
+      // the list stands behind the records (stride is a multiple of 16)
+      uint8_t* const dpairs = s->gscratch + ch.records * stride;
+      step(hipMemcpyAsync(s->gscratch, up, ch.records * stride, hipMemcpyHostToDevice,
+                          s->stream)) &&
+          step(hipMemcpyAsync(dpairs, plan.pairs.data() + ch.pair0,
+                              ch.pairs * sizeof(rs::ScatterPair), hipMemcpyHostToDevice,
+                              s->stream)) &&
+          step(hipEventRecord(s->gev[2 * i], s->stream)) &&
+          step(rs::launch_scatter(s->d, dpairs, (uint32_t)ch.pairs, Y, s->gscratch, s->stream)) &&
+          step(hipEventRecord(s->gev[2 * i + 1], s->stream));
+    }
+  }
+  // every started shard is waited for, also after an error: its uploads read the stages
+  for (size_t d : started) {
+    Shard* s = r->sh[d];
+    step(hipSetDevice(s->cfg.device));
+    const hipError_t e = hipStreamSynchronize(s->stream);   // also when an earlier shard failed
+    step(e);
+    if (rc) continue;
+    double ms = 0;
+    for (size_t i = 0; i < count[d] && !rc; ++i) {
+      float t = 0;
+      if (step(hipEventElapsedTime(&t, s->gev[2 * i], s->gev[2 * i + 1]))) ms += t;
+    }
+    if (!rc) s->scatter_ms = ms;
+  }
+  if (!rc)
+    for (size_t d = 0; d < G; ++d)
+      if (!count[d]) r->sh[d]->scatter_ms = 0;
+  return rc ? rc : (int64_t)n;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_scatter_write's kernels
+// (HIP events around each chunk's kernel on each shard's stream, summed), the maximum over shards,
+// in ms.
+extern "C" int raftsim_diag_scatter_ms(raft_sim_t* r, double* ms) {
+  return diag_ms(r, ms, &Shard::scatter_ms);
 }
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was

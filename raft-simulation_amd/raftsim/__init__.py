@@ -15,7 +15,7 @@ from . import _build
 from ._abi import COUNTER_NAMES  # noqa: F401
 from . import _abi
 from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, ClusterPack, GpuBackend,  # noqa: F401
-                       RaftSimError, replay_config)
+                       RaftSimError, check_pack_fits, replay_config)
 
 PKG_DIR = Path(__file__).resolve().parent.parent          # raft-simulation_amd/
 LIB_PATH = Path(os.environ.get("RAFTSIM_LIB", PKG_DIR / "build" / "libraftsim.so"))
@@ -125,3 +125,74 @@ def fork(source, cluster, **overrides):
     one = Simulator(**cfg)
     one.restore_cluster(pack, i)
     return one
+
+
+def _scattered(pack, who, cfg, records=None):
+    """A Simulator of config `cfg` at the pack's tick whose clusters are the pack's `records`
+    (default: record i for cluster i), written by one scatter."""
+    check_pack_fits(_abi.Config(**cfg), pack, who)
+    sim = Simulator(**cfg)
+    try:
+        sim.set_tick(pack.tick)
+        sim.scatter(pack, range(cfg["n_clusters"]), records)
+    except Exception:
+        sim.close()
+        raise
+    return sim
+
+
+def resume(pack, **overrides):
+    """A Simulator that continues the clusters of a ClusterPack: the pack's config with n_clusters
+    = len(pack) at the global id of the pack's first cluster, one device and the trace rings off
+    (`overrides` replace any field, e.g. n_devices), set to the pack's tick and written by one
+    scatter() on the device. The pack's clusters must be a run of consecutive ascending ids
+    (gather(range(c0, c0 + n))): cluster i of the new handle then has the global id the i-th
+    packed cluster had, so it continues bit-exactly as that cluster does in its source.
+
+    resume(ClusterPack.load(path)) is the checkpoint path: gather(range(sim.C)).save(path) writes
+    a handle's whole state to a file, and this loads it back into a running handle at the speed of
+    the upload. Like fork(), it carries over neither violation records nor counters nor trace
+    `seq` numbers, none of which is state; unlike fork(), it continues any number of clusters."""
+    n = len(pack)
+    if n == 0:
+        raise ValueError("resume: the pack holds no cluster")
+    c0 = pack.clusters[0]
+    if pack.clusters != list(range(c0, c0 + n)):
+        bad = next(i for i, c in enumerate(pack.clusters) if c != c0 + i)
+        raise ValueError(f"resume: the pack's clusters must be consecutive ascending ids; "
+                         f"clusters[{bad}] = {pack.clusters[bad]} follows {pack.clusters[bad - 1]}")
+    cfg = replay_config(_abi.Config(**pack.config), c0, trace_cap=0, trace_entry_cap=0)
+    cfg.update(n_clusters=n)
+    return _scattered(pack, "resume", _override(cfg, overrides))
+
+
+def fan_out(source, cluster, copies, **overrides):
+    """A Simulator of `copies` clusters that all start as one cluster of a snapshot: `source` is a
+    Simulator, whose cluster `cluster` is gathered, or a ClusterPack, of which `cluster` is the
+    position in the pack (as fork() takes them). The new handle has the source's config with
+    n_clusters = copies at cluster_offset = the cluster's global id g, one device and the trace
+    rings off (`overrides` replace any field), is set to the pack's tick, and every cluster of it
+    is scattered from the one record on the device. Philox is keyed by the global cluster id:
+    cluster 0 continues bit-exactly as the original does, and cluster j is that state's future
+    under id g + j -- `copies` independent futures of one state. g + copies must not exceed 2^32
+    (the config's own limit)."""
+    if isinstance(source, ClusterPack):
+        pack, i = source, int(cluster)
+        if not 0 <= i < len(pack):
+            raise ValueError(f"position {i} outside the pack's {len(pack)} clusters")
+    else:
+        pack, i = source.gather([cluster]), 0
+    copies = int(copies)
+    if copies < 1:
+        raise ValueError("fan_out: copies must be >= 1")
+    cfg = replay_config(_abi.Config(**pack.config), pack.clusters[i], trace_cap=0,
+                        trace_entry_cap=0)
+    cfg.update(n_clusters=copies)
+    return _scattered(pack, "fan_out", _override(cfg, overrides), [i] * copies)
+
+
+def _override(cfg, overrides):
+    for k in overrides:
+        if k not in cfg:
+            raise TypeError(f"unknown config field {k!r}")
+    return dict(cfg, **overrides)

@@ -306,6 +306,17 @@ _GATHER_SIGS = {
 GATHER_SYMBOLS = ["raft_gather_" + n for n in _GATHER_SIGS]
 
 
+# The packs' way back (include/raftsim.h, raft_scatter_write): under a prefix of its own, so the
+# raft_gather_* set stays the two read-side calls.
+_SCATTER_SIGS = {
+    "write": (C.c_int64, [C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32, C.c_uint32,
+                          C.c_void_p, C.c_uint32]),
+}
+SCATTER_SYMBOLS = ["raft_scatter_" + n for n in _SCATTER_SIGS]
+# the parts a pack must hold to be written back (and "streams" when commit_stream_cap > 0)
+SCATTER_PARTS = ("cluster", "nodes", "queues", "arenas")
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

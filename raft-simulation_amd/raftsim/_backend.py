@@ -451,6 +451,7 @@ class GpuBackend(Backend):
         self._census = _abi.bind(self._lib, "raft_census_", sigs=_abi._CENSUS_SIGS)
         self._audit = _abi.bind(self._lib, "raft_audit_", sigs=_abi._AUDIT_SIGS)
         self._gather = _abi.bind(self._lib, "raft_gather_", sigs=_abi._GATHER_SIGS)
+        self._scatter = _abi.bind(self._lib, "raft_scatter_", sigs=_abi._SCATTER_SIGS)
 
     # -- what the three device-side queries share ------------------------------------------------
     @staticmethod
@@ -646,12 +647,70 @@ class GpuBackend(Backend):
         """Diagnostic: device time (HIP events) of the last gather()'s kernels."""
         return self._diag_ms("raftsim_diag_gather_ms")
 
+    def scatter(self, pack, clusters=None, records=None):
+        """Write records of a ClusterPack into clusters of this handle on the device
+        (raft_scatter_write): record records[i] of the pack becomes cluster clusters[i]; returns
+        the number of clusters written. `clusters` (handle-local ids, any order, none twice)
+        defaults to pack.clusters, `records` (positions in the pack) to 0..len(clusters)-1 and may
+        name a position any number of times: one record placed at K ids is K futures of that state.
+        The handle must have the pack's nodes, inbox_cap, log_cap, arena_cap and
+        commit_stream_cap, and the pack the parts cluster, nodes, queues and arenas (and streams
+        when commit_stream_cap > 0): ValueError names what is missing. The clock is not set
+        (set_tick does that); violation records, counters and trace rings stay as they are. All or
+        nothing: a refused call (RaftSimError naming the first offending position) wrote nothing."""
+        check_pack_fits(self.config, pack, "scatter")
+        def index_list(xs, name, bound, whose):
+            if not isinstance(xs, np.ndarray):
+                xs = [int(x["cluster"] if isinstance(x, dict) else x) for x in xs]
+            a = np.asarray(xs, dtype=np.int64).reshape(-1)
+            out = np.flatnonzero((a < 0) | (a >= bound))
+            if out.size:
+                raise ValueError(f"{name}[{out[0]}] = {a[out[0]]} is outside {whose} {bound}")
+            return np.ascontiguousarray(a, dtype=np.uint32)
+
+        idx = index_list(pack.clusters if clusters is None else clusters, "clusters", self.C,
+                         "the handle's")
+        n = idx.size
+        if records is None:
+            if n > len(pack):
+                raise ValueError(f"{n} clusters for the pack's {len(pack)} records")
+            rec_ptr = None
+        else:
+            rec = index_list(records, "records", len(pack), "the pack's")
+            if rec.size != n:
+                raise ValueError(f"{rec.size} records for {n} clusters")
+            rec_ptr = rec.ctypes.data_as(C.POINTER(C.c_uint32))
+        mask = self._mask(pack.parts, _abi.GATHER_PARTS, "pack part")
+        self.host_written = True
+        return self._check(int(self._scatter["write"](
+            self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), rec_ptr, n, mask,
+            pack.data.ctypes.data_as(C.c_void_p), len(pack))))
+
+    def last_scatter_ms(self):
+        """Diagnostic: device time (HIP events) of the last scatter()'s kernels."""
+        return self._diag_ms("raftsim_diag_scatter_ms")
+
     def replay_config(self, cluster, **overrides):
         """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster
         `cluster` of this one alone: Philox is keyed by the global cluster id, so n_clusters=1 at
         cluster_offset + cluster reproduces it exactly from init-node. The trace rings are on by
         default (the `wait` trace, F3); `overrides` replace any field."""
         return replay_config(self.config, cluster, **overrides)
+
+
+def check_pack_fits(config, pack, who):
+    """What a pack must be to be written into a handle of `config` (restore_cluster's conditions,
+    needs no library): the parts cluster, nodes, queues, arenas (and streams when the pack keeps
+    commit streams), and the handle's nodes, inbox_cap, log_cap, arena_cap, commit_stream_cap."""
+    for name in list(_abi.SCATTER_PARTS) + (["streams"] if pack.SC else []):
+        if name not in pack.layout:
+            raise ValueError(f"{who} needs the {name!r} part; the pack holds {list(pack.parts)}")
+    mine = (config.nodes, config.inbox_cap, config.log_cap,
+            config.arena_cap or 4 * config.log_cap, config.commit_stream_cap)
+    if mine != (pack.N, pack.Q, pack.L, pack.A, pack.SC):
+        raise ValueError(f"{who}: the handle's nodes, inbox_cap, log_cap, arena_cap, "
+                         f"commit_stream_cap {mine} are not the pack's "
+                         f"{(pack.N, pack.Q, pack.L, pack.A, pack.SC)}")
 
 
 def replay_config(config, cluster, **overrides):

@@ -1,6 +1,6 @@
 # Registers, scratch and occupancy of every tick-kernel instantiation, and of the query kernels
-# (violation records, census, log audit, cluster packs) after them, as the compiler reports them
-# (ISA comments of hipcc -S), written to profiles/TAG_kernel_resources.txt. rocprofv3's
+# (violation records, census, log audit, cluster packs and their scatter) after them, as the
+# compiler reports them (ISA comments of hipcc -S), written to profiles/TAG_kernel_resources.txt. rocprofv3's
 # VGPR_Count column uses a different encoding; these are the compiler's own counts.
 # Usage: bash scripts/kernel_resources.sh TAG
 set -e
@@ -12,6 +12,7 @@ S3=$(mktemp /tmp/violations_kernel_XXXX.s)
 S4=$(mktemp /tmp/census_kernel_XXXX.s)
 S5=$(mktemp /tmp/audit_kernel_XXXX.s)
 S6=$(mktemp /tmp/gather_kernel_XXXX.s)
+S7=$(mktemp /tmp/scatter_kernel_XXXX.s)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S \
   $R/raft-simulation_amd/csrc/tick_kernel.hip 2>/dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S2 \
@@ -24,7 +25,9 @@ S6=$(mktemp /tmp/gather_kernel_XXXX.s)
   $R/raft-simulation_amd/csrc/audit_kernel.hip 2>/dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S6 \
   $R/raft-simulation_amd/csrc/gather_kernel.hip 2>/dev/null
-python3 - "$S" "$S2" "$S3" "$S4" "$S5" "$S6" > $R/profiles/${TAG}_kernel_resources.txt <<'PY'
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o $S7 \
+  $R/raft-simulation_amd/csrc/scatter_kernel.hip 2>/dev/null
+python3 - "$S" "$S2" "$S3" "$S4" "$S5" "$S6" "$S7" > $R/profiles/${TAG}_kernel_resources.txt <<'PY'
 import re, sys
 s = ''.join(open(f).read() for f in sys.argv[1:])
 print(f"{'kernel':48s} {'VGPRs':>5s} {'SGPRs':>5s} {'scratch':>7s} {'waves/SIMD':>10s}")
@@ -41,7 +44,7 @@ for m in re.finditer(r'^(_ZN2rs\w+):\s', s, re.M):
     ml = re.match(r'rs::18steady_lane_kernelILi(\d)E', pretty)
     if ml:
         pretty = f"steady_lane_kernel<N={ml.group(1)}>"
-    mc = re.match(r'rs::\d+((?:census|viol|audit|gather)_\w*?kernel)E', pretty)
+    mc = re.match(r'rs::\d+((?:census|viol|audit|gather|scatter)_\w*?kernel)E', pretty)
     if mc:
         pretty = mc.group(1)
     mf = re.match(r'rs::19summary_fold_kernelI\d+raft_([a-z]+)E', pretty)
@@ -56,5 +59,5 @@ for m in re.finditer(r'^(_ZN2rs\w+):\s', s, re.M):
         pretty = mq.group(1) + (f"<{mq.group(2)}>" if mq.group(2) else "")
     print(f"{pretty[:48]:48s} {get('NumVgprs'):>5s} {get('TotalNumSgprs'):>5s} {get('ScratchSize'):>7s} {get('Occupancy'):>10s}")
 PY
-rm -f $S $S2 $S3 $S4 $S5 $S6
+rm -f $S $S2 $S3 $S4 $S5 $S6 $S7
 cat $R/profiles/${TAG}_kernel_resources.txt

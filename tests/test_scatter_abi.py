@@ -1,0 +1,122 @@
+"""The scatter of cluster packs without a GPU: the ABI extension (raft_scatter_write: the header,
+the exported symbols, the argument checks that come before the handle is looked at, the Clojure
+facade's view) and the refusals of raftsim.scatter's callers that precede any handle."""
+import ctypes
+import re
+import subprocess
+from pathlib import Path
+
+import pytest
+
+import gather_mirror as gm
+import helpers
+import raftsim
+from raftsim import _abi, _build
+from test_gather_abi import ROUNDTRIP, run_oracle
+
+ROOT = Path(__file__).resolve().parent.parent
+HEADER = (ROOT / "include" / "raftsim.h").read_text()
+CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
+BIT = _abi.GATHER_PARTS
+NEED = BIT["cluster"] | BIT["nodes"] | BIT["queues"] | BIT["arenas"]
+
+
+def test_header_declares_the_scatter():
+    assert sorted(set(re.findall(r"\b(raft_scatter_\w+)\s*\(", HEADER))) == \
+        sorted(_abi.SCATTER_SYMBOLS) == ["raft_scatter_write"]
+    assert "#define RAFT_SIM_ABI_VERSION 2" in HEADER      # an addition
+    # the read side's names are the two they were
+    assert sorted(set(re.findall(r"\b(raft_gather_\w+)\s*\(", HEADER))) == \
+        sorted(_abi.GATHER_SYMBOLS) == ["raft_gather_layout", "raft_gather_read"]
+    decl = re.search(r"int64_t raft_scatter_write\((.*?)\);", HEADER, re.S).group(1)
+    assert [a.split()[-1].lstrip("*") for a in decl.split(",")] == \
+        ["sim", "clusters", "records", "n", "parts", "in", "n_records"]
+    res, args = _abi._SCATTER_SIGS["write"]
+    assert res is ctypes.c_int64 and len(args) == 7
+    # the kernel and the host header are part of the build and of its hash
+    assert "raft-simulation_amd/csrc/scatter_kernel.hip" in _build.KERNEL_SOURCES
+    assert "raft-simulation_amd/csrc/scatter_host.hpp" in _build.KERNEL_SOURCES
+    entry = (ROOT / "__graft_entry__.py").read_text()
+    assert '"scatter_kernel.hip"' in re.search(r"HIP_SOURCES = \[(.*?)\]", entry, re.S).group(1)
+    # no oracle counterpart
+    with helpers.oracle(n_clusters=1) as h:
+        assert not hasattr(h, "scatter") and hasattr(h, "restore_cluster")
+
+
+def test_library_exports_exactly_the_scatter_entry_point():
+    assert raftsim.LIB_PATH.exists(), "run __graft_entry__.build() first"
+    out = subprocess.run(["nm", "-D", "--defined-only", str(raftsim.LIB_PATH)],
+                         capture_output=True, text=True, check=True).stdout
+    assert set(re.findall(r"\bT (raft_scatter_\w+)", out)) == set(_abi.SCATTER_SYMBOLS)
+    assert "T raftsim_diag_scatter_ms" in out
+    assert set(re.findall(r"\bT (raft_gather_\w+)", out)) == {"raft_gather_layout",
+                                                            "raft_gather_read"}
+
+
+def test_clojure_facade_names_the_entry_point():
+    assert set(re.findall(r'"(raft_scatter_\w+)"', CLJ)) == set(_abi.SCATTER_SYMBOLS)
+    assert "(defn scatter\n" in CLJ
+    assert set(re.findall(r'"(raft_gather_\w+)"', CLJ)) == set(_abi.GATHER_SYMBOLS)
+
+
+def test_bad_arguments_are_refused_without_a_device():
+    lib = ctypes.CDLL(str(raftsim.LIB_PATH))        # loads without a GPU
+    write = _abi.bind(lib, "raft_scatter_", sigs=_abi._SCATTER_SIGS)["write"]
+    last_error = _abi.bind(lib, "raft_sim_")["last_error"]
+    idx = (ctypes.c_uint32 * 4)(0, 1, 2, 3)
+    buf = ctypes.create_string_buffer(64)
+    assert write(None, idx, None, 4, 63, buf, 4) == -22 and b"null sim" in last_error()
+    # parts and the pointers are checked before the handle is looked at: a handle that is never
+    # dereferenced stands in for a live one
+    fake = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(64)))
+    for parts in (0, 64, 2 ** 32 - 1):
+        assert write(fake, idx, None, 4, parts, buf, 4) == -22, parts
+        assert b"RAFT_GATHER_ALL" in last_error()
+    for name in _abi.SCATTER_PARTS:
+        assert write(fake, idx, None, 4, 63 & ~BIT[name], buf, 4) == -22, name
+        assert f"RAFT_GATHER_{name.upper()}".encode() in last_error()
+    assert write(fake, idx, None, 4, BIT["logs"], buf, 4) == -22
+    assert write(fake, None, None, 4, NEED, buf, 4) == -22 and b"null cluster list" in last_error()
+    assert write(fake, idx, idx, 4, NEED, None, 4) == -22 and b"null input" in last_error()
+    ms = ctypes.c_double()
+    lib.raftsim_diag_scatter_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    assert lib.raftsim_diag_scatter_ms(None, ctypes.byref(ms)) == -22
+
+
+def test_python_refusals_before_any_handle():
+    h = run_oracle(dict(ROUNDTRIP, n_clusters=4), 100)
+    for missing in _abi.SCATTER_PARTS:
+        pack = gm.pack_of(h, [0, 1], [p for p in gm.PARTS if p != missing])
+        for call in (lambda: raftsim.resume(pack), lambda: raftsim.fan_out(pack, 0, 8)):
+            with pytest.raises(ValueError, match=f"needs the '{missing}' part"):
+                call()
+    s = run_oracle(dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4), 100)
+    with pytest.raises(ValueError, match="'streams'"):
+        raftsim.resume(gm.pack_of(s, [0], gm.PARTS[:-1]))
+    # a pack resumes as a run of consecutive ascending ids only
+    for ids, bad in (([0, 2], 1), ([1, 0], 1), ([0, 1, 1], 2), ([3, 2, 1], 1)):
+        with pytest.raises(ValueError, match=rf"consecutive ascending ids; clusters\[{bad}\]"):
+            raftsim.resume(gm.pack_of(h, ids))
+    with pytest.raises(ValueError, match="no cluster"):
+        raftsim.resume(gm.pack_of(h, []))
+    full = gm.pack_of(h, [1, 2])
+    with pytest.raises(TypeError, match="unknown config field"):
+        raftsim.resume(full, nonsense=1)
+    with pytest.raises(ValueError, match="log_cap"):
+        raftsim.resume(full, log_cap=32)
+    with pytest.raises(ValueError, match="outside the pack"):
+        raftsim.fan_out(full, 2, 8)
+    with pytest.raises(ValueError, match="copies"):
+        raftsim.fan_out(full, 0, 0)
+    # the config the two would make (no library needed)
+    cfg = raftsim.replay_config(_abi.Config(**full.config), 1, trace_cap=0, trace_entry_cap=0)
+    assert (cfg["cluster_offset"], cfg["n_devices"], cfg["trace_cap"]) == (1, 1, 0)
+
+
+def test_fan_out_past_the_last_global_id_is_the_configs_error():
+    """g + copies > 2^32: raft_sim_create's own refusal, which precedes every device call."""
+    h = run_oracle(dict(ROUNDTRIP, n_clusters=2, cluster_offset=2 ** 32 - 2), 100)
+    pack = gm.pack_of(h, [1])
+    assert pack.global_ids == [2 ** 32 - 1]
+    with pytest.raises(raftsim.RaftSimError, match=r"cluster_offset \+ n_clusters"):
+        raftsim.fan_out(pack, 0, 2)
