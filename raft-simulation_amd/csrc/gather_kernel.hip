@@ -3,14 +3,13 @@
 // packs"; the layout: raft_gather_layout_t). Reads state only.
 //
 // Mapping: `splits` workgroups of four waves per record, the groups of workgroups striding over the
-// list of (cluster, output slot) pairs. The clusters come from anywhere in the shard, so nothing is
-// shared between records; inside a record every part is a flat array whose elements the lanes of
-// the record's workgroups take in order (workgroup s of a record the s-th 256 of every splits *
-// 256), adjacent lanes on adjacent bytes of the record. A record of a few KB has one workgroup; a
-// 1.5-MB record (N = 9, 16,384-slot arenas), of which a 64-MiB scratch holds 45, has 46, since 45
-// workgroups would leave most of the chip idle (launch_gather):
-//   - the node records are decoded word by word (34 words each, one dword per lane), with the hot
-//     block's accessors; an owed timer draw is resolved as every reader of the state resolves it;
+// list of (cluster, output slot) pairs (pack.hpp: the launch shape and a workgroup's share, which
+// scatter_kernel.hip uses too). The clusters come from anywhere in the shard, so nothing is shared
+// between records; inside a record every part is a flat array whose elements the lanes of the
+// record's workgroups take in order, adjacent lanes on adjacent bytes of the record:
+//   - the node records are decoded word by word (34 words each, one dword per lane) by
+//     node_codec.hpp's node_word, which raft_sim_read_nodes uses too; an owed timer draw is
+//     resolved as every reader of the state resolves it;
 //   - queues, logs and arenas move 16 bytes per lane: a message is two uint4 of a ring slot (rings
 //     are 32-byte aligned), a log or arena chunk is two 8-byte entries. Two entries are one uint4
 //     load where they are neighbours in the arena at an even slot, and two uint2 loads where the
@@ -20,83 +19,22 @@
 // What a node's parts need of its hot words (counts, ring heads, the arena offset) is read once per
 // record into LDS. A record's padding is written as zeros with the part before it, so the kernel
 // writes every byte of a record and the scratch needs no clearing.
-#include <stddef.h>
-
-#include <algorithm>
-
-#include "device.hpp"
+#include "pack.hpp"
 
 namespace rs {
 
-constexpr uint32_t GATHER_BLOCK = 256;
-constexpr uint32_t GATHER_MAX_GRID = 4096;       // records in flight
-constexpr uint32_t GATHER_SPLIT_BYTES = 32768;   // a workgroup's share of a record, at least
-constexpr uint32_t GATHER_MAX_SPLITS = 64;
-constexpr uint32_t NODE_WORDS = sizeof(raft_node_t) / 4;
-static_assert(sizeof(raft_node_t) == 136 && sizeof(raft_msg_t) == 32 && sizeof(raft_entry_t) == 8 &&
-                  sizeof(raft_cluster_t) == 32,
-              "the record sizes the pack's layout is made of");
-static_assert(offsetof(raft_node_t, votes) == 6 && offsetof(raft_node_t, ls_keys) == 8 &&
-                  offsetof(raft_node_t, current_term) == 12 && offsetof(raft_node_t, deadline) == 24 &&
-                  offsetof(raft_node_t, next_index) == 28 && offsetof(raft_node_t, match_index) == 64 &&
-                  offsetof(raft_node_t, last_led_term) == 100 &&
-                  offsetof(raft_node_t, req_count) == 112 &&
-                  offsetof(raft_node_t, commit_count) == 120 &&
-                  offsetof(raft_node_t, trace_hash) == 128,
-              "gather_node_word's word numbers");
-
-// Word w (0..33) of node k's raft_node_t, as raft_sim_read_nodes decodes it. cc: its commit_count.
-__device__ __forceinline__ uint32_t gather_node_word(const DevSim& S, uint32_t c, uint32_t k,
-                                                     uint32_t w, uint32_t cc) {
-  const uint32_t N = S.N;
-  const uint32_t* const h = hot_node(S, c, k);         // field f at h[f * N]
-  if (w >= 7 && w < 7 + 2 * RAFT_MAX_NODES) {           // next_index, then match_index
-    const uint32_t row = w >= 7 + RAFT_MAX_NODES, p = w - 7 - row * RAFT_MAX_NODES;
-    return p < N ? h[(HF_NEXT + row * N + p) * N] : 0u;
-  }
-  switch (w) {
-    case 0: {
-      const uint32_t fl = h[HF_FLAGS * N];
-      return fl_role(fl) | fl_vf(fl) << 8 | fl_lid(fl) << 16 | fl_fault(fl) << 24;
-    }
-    case 1: {
-      const uint32_t fl = h[HF_FLAGS * N];
-      return fl_seq(fl) | fl_lsp(fl) << 8 | (h[HF_MASKS * N] & 0xFFFFu) << 16;
-    }
-    case 2: return h[HF_MASKS * N] >> 16;               // ls_keys; reserved0 is zero
-    case 3: return h[HF_TERM * N];
-    case 4: return h[HF_COMMIT * N];
-    case 5: return h[HF_LEN * N];
-    case 6: {
-      const uint32_t dl = h[HF_DEADLINE * N];
-      return h[HF_FLAGS * N] & FL_DRAW
-                 ? exact_deadline(S.goff + c, k + 1, dl, S.el_base, S.el_span, S.key0, S.key1)
-                 : dl;
-    }
-    case 25: return h[hf_led(N) * N];
-    case 26: return h[hf_abase(N) * N];
-    case 27: return h[hf_afront(N) * N];
-    case 28: return qm_req_cnt(h[HF_QMETA * N]);
-    case 29: return qm_res_cnt(h[HF_QMETA * N]);
-    case 30: return cc;
-    case 32: return h[HF_TRACE_LO * N];
-    case 33: return h[HF_TRACE_HI * N];
-    default: return 0u;                                 // 31: the padding before trace_hash
-  }
-}
-
 // Y.off[b]: byte offset of part bit b in a record, UINT64_MAX where the part is not asked for.
-__global__ void __launch_bounds__(GATHER_BLOCK)
+__global__ void __launch_bounds__(PACK_BLOCK)
 gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint32_t splits,
               const raft_gather_layout_t Y, uint8_t* __restrict__ out) {
   __shared__ uint32_t s_qm[RAFT_MAX_NODES], s_len[RAFT_MAX_NODES], s_off[RAFT_MAX_NODES],
       s_cc[RAFT_MAX_NODES];
   const uint32_t N = S.N, Q = S.Q, L = S.L, A = S.A, SC = S.SC, tid = threadIdx.x;
   const uint4 zero4 = make_uint4(0, 0, 0, 0);
-  // this workgroup's lanes' first element of every part, and their step
-  const uint32_t sp = blockIdx.x % splits, first = sp * GATHER_BLOCK + tid;
-  const uint32_t step = splits * GATHER_BLOCK;
-  for (uint32_t r = blockIdx.x / splits; r < n; r += gridDim.x / splits) {
+  const DrawKeys dk = {S.el_base, S.el_span, S.key0, S.key1};
+  const PackLanes ln(splits);
+  const uint32_t first = ln.first, step = ln.step;
+  for (uint32_t r = ln.r0; r < n; r += ln.rstep) {
     const uint32_t c = pairs[r].x;
     if (c >= S.C) continue;                              // (the host refuses such a list)
     uint8_t* const rec = out + (size_t)pairs[r].y * Y.stride;
@@ -121,8 +59,8 @@ gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint3
       uint32_t* const o = reinterpret_cast<uint32_t*>(rec + Y.off[1]);
       const uint32_t words = N * NODE_WORDS, padded = (words + 3) & ~3u;
       for (uint32_t i = first; i < padded; i += step) {
-        const uint32_t k = i / NODE_WORDS;
-        o[i] = i < words ? gather_node_word(S, c, k, i - k * NODE_WORDS, s_cc[k]) : 0u;
+        const uint32_t k = i / NODE_WORDS, w = i - k * NODE_WORDS;
+        o[i] = i < words ? node_word(hot_node(S, c, k), N, w, s_cc[k], S.goff + c, k, dk) : 0u;
       }
     }
 
@@ -130,15 +68,15 @@ gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint3
       uint4* const o = reinterpret_cast<uint4*>(rec + Y.off[2]);
       const uint32_t total = N * 2 * Q * 2;              // halves of messages
       for (uint32_t i = first; i < total; i += step) {
-        const uint32_t half = i & 1, m = i >> 1, ring = m / Q, p = m - ring * Q;
-        const uint32_t k = ring >> 1, which = ring & 1, qm = s_qm[k];
-        const uint32_t head = which ? qm_res_head(qm) : qm_req_head(qm);
-        const uint32_t cnt = min(which ? qm_res_cnt(qm) : qm_req_cnt(qm), Q);
+        const QueueElem e = queue_elem(i, Q);
+        const uint32_t qm = s_qm[e.k];
+        const uint32_t head = e.which ? qm_res_head(qm) : qm_req_head(qm);
+        const uint32_t cnt = min(e.which ? qm_res_cnt(qm) : qm_req_cnt(qm), Q);
         uint4 v = zero4;
-        if (p < cnt) {
-          const uint32_t slot = (head + p) % Q;
-          v = reinterpret_cast<const uint4*>(qslots(S, c * N + k, (int)which) +
-                                             slot * qstride(S, (int)which))[half];
+        if (e.p < cnt) {
+          const uint32_t slot = (head + e.p) % Q;
+          v = reinterpret_cast<const uint4*>(qslots(S, c * N + e.k, (int)e.which) +
+                                             slot * qstride(S, (int)e.which))[e.half];
         }
         o[i] = v;
       }
@@ -161,8 +99,7 @@ gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint3
           s[j] = k * A + t;                              // < N A <= 9 * 2^24
           e[j] = make_uint2(0, 0);
         }
-        const bool src16 = (((size_t)c * N * A + s[0]) & 1) == 0;
-        if (ok[0] && ok[1] && s[1] == s[0] + 1 && src16) {
+        if (ok[0] && ok[1] && s[1] == s[0] + 1 && arena_even(S, c, s[0])) {
           const uint4 v = *reinterpret_cast<const uint4*>(ar + s[0]);
           e[0] = make_uint2(v.x, v.y);
           e[1] = make_uint2(v.z, v.w);
@@ -178,7 +115,7 @@ gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint3
       uint4* const o = reinterpret_cast<uint4*>(rec + Y.off[4]);
       const uint32_t entries = N * A, chunks = (entries + 1) >> 1;
       const uint2* const ar = arena_of(S, c * N);
-      const bool src16 = (((size_t)c * N * A) & 1) == 0; // the cluster's first slot is even
+      const bool src16 = arena_even(S, c, 0);
       for (uint32_t i = first; i < chunks; i += step) {
         uint4 v;
         if (src16 && 2 * i + 1 < entries) {
@@ -212,11 +149,9 @@ gather_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint3
 hipError_t launch_gather(const DevSim& S, const void* pairs, uint32_t n,
                          const raft_gather_layout_t& Y, void* out, hipStream_t st) {
   if (!n) return hipSuccess;
-  const uint32_t splits = (uint32_t)std::min<uint64_t>(
-      std::max<uint64_t>(Y.stride / GATHER_SPLIT_BYTES, 1), GATHER_MAX_SPLITS);
-  hipLaunchKernelGGL(gather_kernel, dim3(std::min(n, GATHER_MAX_GRID) * splits), dim3(GATHER_BLOCK),
-                     0, st, S, static_cast<const uint2*>(pairs), n, splits, Y,
-                     static_cast<uint8_t*>(out));
+  const uint32_t splits = pack_splits(Y.stride);
+  hipLaunchKernelGGL(gather_kernel, pack_grid(n, splits), dim3(PACK_BLOCK), 0, st, S,
+                     static_cast<const uint2*>(pairs), n, splits, Y, static_cast<uint8_t*>(out));
   return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "device.hpp"
+#include "node_codec.hpp"
 #include "scatter_host.hpp"
 #include "summary_host.hpp"
 
@@ -148,7 +148,8 @@ struct Shard {
   std::vector<hipEvent_t> gev;
   double gather_ms;
   // raft_scatter_write (scatter_kernel.hip) uploads its records and lists into the same scratch and
-  // times its chunks' kernels with the same events (raftsim_diag_scatter_ms).
+  // times its chunks' kernels with the same events (raftsim_diag_scatter_ms); pack_scratch,
+  // pack_events and pack_wait below serve both calls.
   double scatter_ms;
 };
 constexpr uint32_t STEADY_COOLDOWN = 2;
@@ -569,30 +570,13 @@ static int sh_read_nodes(Shard* s, uint32_t c0, uint32_t nc, raft_node_t* out) {
   HIP_OK(d2h(s, blk.data(), s->d.hot + (size_t)c0 * HB, nc * HB));
   HIP_OK(d2h(s, cc.data(), s->d.ccount + n0, cnt));
   HIP_OK(hipStreamSynchronize(s->stream));
+  const rs::DrawKeys dk = {s->cfg.el_base, s->cfg.el_span, s->d.key0, s->d.key1};
   for (size_t i = 0; i < cnt; ++i) {
-    const uint32_t* h = &blk[(i / N) * HB + rs::HOT_CW + i % N];     // field f at h[f * N]
-    auto f = [&](uint32_t fld) { return h[fld * N]; };
-    raft_node_t& r = out[i];
-    memset(&r, 0, sizeof r);
-    const uint32_t fl = f(rs::HF_FLAGS), mk = f(rs::HF_MASKS), qm = f(rs::HF_QMETA);
-    r.role = rs::fl_role(fl); r.voted_for = rs::fl_vf(fl); r.leader_id = rs::fl_lid(fl);
-    r.fault = rs::fl_fault(fl); r.entries_is_seq = rs::fl_seq(fl); r.ls_present = rs::fl_lsp(fl);
-    r.votes = mk & 0xFFFF; r.ls_keys = mk >> 16;
-    r.current_term = f(rs::HF_TERM); r.commit_index = f(rs::HF_COMMIT);
-    r.log_len = f(rs::HF_LEN); r.deadline = f(rs::HF_DEADLINE);
-    if (fl & rs::FL_DRAW)        // a deferred timer draw still owed in the stored state
-      r.deadline = rs::exact_deadline((uint32_t)(s->cfg.cluster_offset + c0 + i / N),
-                                      (uint32_t)(i % N) + 1, r.deadline, s->cfg.el_base,
-                                      s->cfg.el_span, s->d.key0, s->d.key1);
-    for (size_t p = 0; p < N; ++p) {
-      r.next_index[p] = (int32_t)f(rs::HF_NEXT + p);
-      r.match_index[p] = (int32_t)f(rs::HF_NEXT + N + p);
-    }
-    r.last_led_term = f(rs::hf_led(N));
-    r.arena_base = f(rs::hf_abase(N)); r.arena_frontier = f(rs::hf_afront(N));
-    r.req_count = rs::qm_req_cnt(qm); r.res_count = rs::qm_res_cnt(qm);
-    r.trace_hash = (uint64_t)f(rs::HF_TRACE_HI) << 32 | f(rs::HF_TRACE_LO);
-    r.commit_count = cc[i];
+    const uint32_t k = (uint32_t)(i % N), g = (uint32_t)(s->cfg.cluster_offset + c0 + i / N);
+    uint32_t nw[rs::NODE_WORDS];
+    for (uint32_t w = 0; w < rs::NODE_WORDS; ++w)
+      nw[w] = rs::node_word(&blk[(i / N) * HB + rs::HOT_CW + k], (uint32_t)N, w, cc[i], g, k, dk);
+    memcpy(&out[i], nw, sizeof nw);
   }
   return 0;
 }
@@ -615,22 +599,12 @@ static int sh_write_nodes(Shard* s, uint32_t c0, uint32_t nc, const raft_node_t*
   HIP_OK(d2h(s, blk.data(), s->d.hot + (size_t)c0 * HB, nc * HB));
   HIP_OK(hipStreamSynchronize(s->stream));
   for (size_t i = 0; i < cnt; ++i) {
-    const raft_node_t& r = in[i];
-    uint32_t* h = &blk[(i / N) * HB + rs::HOT_CW + i % N];
-    auto f = [&](uint32_t fld) -> uint32_t& { return h[fld * N]; };
-    f(rs::HF_FLAGS) = rs::pack_flags(r.role, r.voted_for, r.leader_id, r.fault, r.entries_is_seq,
-                                     r.ls_present);
-    f(rs::HF_MASKS) = r.votes | (uint32_t)r.ls_keys << 16;
-    f(rs::HF_TERM) = r.current_term; f(rs::HF_COMMIT) = r.commit_index;
-    f(rs::HF_LEN) = r.log_len; f(rs::HF_DEADLINE) = r.deadline;
-    f(rs::hf_abase(N)) = r.arena_base; f(rs::hf_afront(N)) = r.arena_frontier;
-    f(rs::hf_led(N)) = r.last_led_term;
-    f(rs::HF_TRACE_LO) = (uint32_t)r.trace_hash; f(rs::HF_TRACE_HI) = (uint32_t)(r.trace_hash >> 32);
-    ccv[i] = r.commit_count;
-    for (size_t p = 0; p < N; ++p) {
-      f(rs::HF_NEXT + p) = (uint32_t)r.next_index[p];
-      f(rs::HF_NEXT + N + p) = (uint32_t)r.match_index[p];
-    }
+    uint32_t nw[rs::NODE_WORDS];
+    memcpy(nw, &in[i], sizeof nw);
+    uint32_t* h = &blk[(i / N) * HB + rs::HOT_CW + i % N];           // field f at h[f * N]
+    for (uint32_t f = 0; f < rs::hot_fields(N); ++f)
+      if (!rs::hf_is_queue(f)) h[f * N] = rs::hot_field(nw, N, f);
+    ccv[i] = in[i].commit_count;
   }
   for (size_t c = 0; c < nc; ++c) blk[c * HB + rs::CL_CERT] = 0;   // the steady certificate
   HIP_OK(h2d(s, s->d.hot + (size_t)c0 * HB, blk.data(), nc * HB));
@@ -679,15 +653,16 @@ static int sh_write_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t whic
   uint32_t qm = 0;
   HIP_OK(d2h(s, &qm, hot_word(s, cluster, id, rs::HF_QMETA), 1));
   HIP_OK(hipStreamSynchronize(s->stream));
-  if (which) qm = (qm & ~rs::QM_RES) | rs::pack_qmeta(0, 0, 0, count);
-  else qm = (qm & ~rs::QM_REQ) | rs::pack_qmeta(0, count, 0, 0);
-  const uint32_t harr = count ? in[0].arrival : rs::INF, tail = count ? in[count - 1].arrival : 0;
+  const rs::RingWords ring = rs::ring_words(which, count, reinterpret_cast<const uint32_t*>(in));
+  qm = rs::with_ring(qm, ring);                                   // the other ring's half stays
   HIP_OK(hipMemcpy2DAsync(qring(s, gi, which), qpitch(s, which), slots.data(),
                           sizeof(raft_msg_t), sizeof(raft_msg_t), s->Q, hipMemcpyHostToDevice,
                           s->stream));
   HIP_OK(h2d(s, hot_word(s, cluster, id, rs::HF_QMETA), &qm, 1));
-  HIP_OK(h2d(s, hot_word(s, cluster, id, which ? rs::HF_RES_ARR : rs::HF_REQ_ARR), &harr, 1));
-  HIP_OK(h2d(s, hot_word(s, cluster, id, which ? rs::HF_RES_TAIL : rs::HF_REQ_TAIL), &tail, 1));
+  const uint32_t farr = which ? rs::HF_RES_ARR : rs::HF_REQ_ARR;
+  const uint32_t ftail = which ? rs::HF_RES_TAIL : rs::HF_REQ_TAIL;
+  HIP_OK(h2d(s, hot_word(s, cluster, id, farr), &ring.arr, 1));
+  HIP_OK(h2d(s, hot_word(s, cluster, id, ftail), &ring.tail, 1));
   const uint32_t zero = 0;                                        // the steady certificate
   HIP_OK(h2d(s, cl_words(s, cluster) + rs::CL_CERT, &zero, 1));
   HIP_OK(hipStreamSynchronize(s->stream));
@@ -1016,9 +991,12 @@ int raft_sim_last_span(raft_sim_t* r, double* span_ms) {
   return 0;
 }
 
-// The shard owning cluster c, and c's index inside it.
+// The index of the shard owning cluster c; the shard, and c's index inside it.
+static size_t owner_index(const raft_sim* r, uint32_t c) {
+  return std::upper_bound(r->lo.begin() + 1, r->lo.end() - 1, c) - (r->lo.begin() + 1);
+}
 static Shard* owner(raft_sim* r, uint32_t c, uint32_t* lc) {
-  const size_t d = std::upper_bound(r->lo.begin() + 1, r->lo.end() - 1, c) - (r->lo.begin() + 1);
+  const size_t d = owner_index(r, c);
   *lc = c - r->lo[d];
   return r->sh[d];
 }
@@ -1404,7 +1382,8 @@ extern "C" int raftsim_diag_audit_ms(raft_sim_t* r, double* ms) {
 // into the caller's buffer where the shard's clusters stand at consecutive positions of the list
 // (always, on one device), else into a host buffer whose records are moved to their positions once
 // the shard is done. Like the census it touches neither the state nor the host's bookkeeping of it
-// (storm_until, keys_written, lite, audit_valid, the steady path choice).
+// (storm_until, keys_written, lite, audit_valid, the steady path choice). The check of the list,
+// the scratch, the events and the wait for a started shard are the pack calls' shared helpers.
 constexpr uint64_t GATHER_SCRATCH_BYTES = 64ull << 20;
 
 static void gather_layout_of(const Shard* s, uint32_t parts, raft_gather_layout_t* y) {
@@ -1439,6 +1418,74 @@ int raft_gather_layout(raft_sim_t* r, uint32_t parts, raft_gather_layout_t* out)
   return 0;
 }
 
+// What raft_gather_read and raft_scatter_write (the pack calls) share on the host.
+
+// Position i of a pack call's cluster list lies in the handle.
+static int pack_cluster_ok(const raft_sim* r, const uint32_t* clusters, uint32_t i) {
+  if (clusters[i] < r->cfg.n_clusters) return 0;
+  char what[96];
+  snprintf(what, sizeof what, "clusters[%u] = %u is outside the handle's %u clusters", i,
+           clusters[i], r->cfg.n_clusters);
+  return fail(-EINVAL, "%s", what);
+}
+
+// The HIP calls of a pack call `who`: the first failure becomes the call's return code, with
+// who's name in the text, and every later step is skipped.
+struct PackCall {
+  const char* who;
+  int rc = 0;
+  void failed(int code, const char* what, hipError_t e) {
+    char text[sizeof g_err];
+    snprintf(text, sizeof text, "%s in %s: %s", what, who, hipGetErrorString(e));
+    rc = fail(code, "%s", text);
+  }
+  bool step(hipError_t e) {
+    if (!rc && e != hipSuccess) failed(-EIO, "HIP error", e);
+    return !rc;
+  }
+};
+
+// The shard's scratch holds `need` bytes (a larger one is made once the stream is done with the
+// smaller), and the shard has an event pair for each of `chunks` kernels.
+static bool pack_scratch(PackCall& p, Shard* s, size_t need) {
+  if (s->gscratch_bytes >= need) return true;
+  if (!p.step(hipStreamSynchronize(s->stream))) return false;
+  if (s->gscratch) (void)hipFree(s->gscratch);
+  s->gscratch = nullptr;
+  s->gscratch_bytes = 0;
+  void* v = nullptr;
+  const hipError_t e = hipMalloc(&v, need);
+  if (e != hipSuccess) {
+    p.failed(-ENOMEM, "hipMalloc failed", e);
+    return false;
+  }
+  s->gscratch = static_cast<uint8_t*>(v);
+  s->gscratch_bytes = need;
+  return true;
+}
+static bool pack_events(PackCall& p, Shard* s, size_t chunks) {
+  while (!p.rc && s->gev.size() < 2 * chunks) {
+    hipEvent_t e;
+    if (p.step(hipEventCreate(&e))) s->gev.push_back(e);
+  }
+  return !p.rc;
+}
+
+// Wait for a started shard -- also after an error, of this shard or of an earlier one: its copies
+// read or write the caller's buffers and the stages -- and, when all went well, make the summed
+// kernel times of its `chunks` event pairs its *ms.
+static bool pack_wait(PackCall& p, Shard* s, size_t chunks, double Shard::*ms) {
+  p.step(hipSetDevice(s->cfg.device));
+  p.step(hipStreamSynchronize(s->stream));
+  double sum = 0;
+  for (size_t ch = 0; ch < chunks && !p.rc; ++ch) {
+    float t = 0;
+    if (p.step(hipEventElapsedTime(&t, s->gev[2 * ch], s->gev[2 * ch + 1]))) sum += t;
+  }
+  if (!p.rc) s->*ms = sum;
+  return !p.rc;
+}
+
 // One shard's share of a raft_gather_read.
 struct GatherJob {
   std::vector<uint2> pairs;     // (shard-local cluster, slot in its chunk's scratch)
@@ -1456,12 +1503,7 @@ int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, ui
   if (n && !clusters) return fail(-EINVAL, "null cluster list");
   if (n && !out) return fail(-EINVAL, "null output");
   for (uint32_t i = 0; i < n; ++i)
-    if (clusters[i] >= r->cfg.n_clusters) {
-      char what[96];
-      snprintf(what, sizeof what, "clusters[%u] = %u is outside the handle's %u clusters", i,
-               clusters[i], r->cfg.n_clusters);
-      return fail(-EINVAL, "%s", what);
-    }
+    if ((rc = pack_cluster_ok(r, clusters, i))) return rc;
   raft_gather_layout_t Y;
   gather_layout_of(r->sh[0], parts, &Y);
   const uint64_t stride = Y.stride, bytes = (uint64_t)n * stride;   // stride < 2^31: no overflow
@@ -1472,23 +1514,17 @@ int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, ui
   const size_t G = r->sh.size();
   std::vector<GatherJob> job(G);
   for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t c = clusters[i];
-    const size_t d = G == 1 ? 0 : std::upper_bound(r->lo.begin() + 1, r->lo.end() - 1, c) -
-                                      (r->lo.begin() + 1);
-    job[d].pairs.push_back(make_uint2(c - r->lo[d], 0));
+    const size_t d = owner_index(r, clusters[i]);
+    job[d].pairs.push_back(make_uint2(clusters[i] - r->lo[d], 0));
     job[d].pos.push_back(i);
   }
   // records and their list entries share the scratch: stride + 8 bytes each, one record at least
   const uint32_t per_chunk =
       (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(GATHER_SCRATCH_BYTES / (stride + 8), n));
   uint8_t* const dst = static_cast<uint8_t*>(out);
-  auto step = [&](hipError_t e) {
-    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_gather_read: %s",
-                                          hipGetErrorString(e));
-    return !rc;
-  };
+  PackCall hip = {"raft_gather_read"};
   size_t started = 0;
-  for (size_t d = 0; d < G && !rc; ++d) {
+  for (size_t d = 0; d < G && !hip.rc; ++d) {
     Shard* s = r->sh[d];
     GatherJob& j = job[d];
     const size_t m = j.pairs.size();
@@ -1504,37 +1540,20 @@ int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, ui
     j.per_chunk = (uint32_t)std::min<size_t>(per_chunk, m);
     j.chunks = (uint32_t)((m + j.per_chunk - 1) / j.per_chunk);
     for (size_t i = 0; i < m; ++i) j.pairs[i].y = (uint32_t)(i % j.per_chunk);
-    if (!step(hipSetDevice(s->cfg.device))) break;
-    const size_t need = (size_t)j.per_chunk * (stride + 8);
-    if (s->gscratch_bytes < need) {
-      if (!step(hipStreamSynchronize(s->stream))) break;
-      if (s->gscratch) (void)hipFree(s->gscratch);
-      s->gscratch = nullptr;
-      s->gscratch_bytes = 0;
-      void* v = nullptr;
-      const hipError_t e = hipMalloc(&v, need);
-      if (e != hipSuccess) {
-        rc = fail(-ENOMEM, "hipMalloc failed in raft_gather_read: %s", hipGetErrorString(e));
-        break;
-      }
-      s->gscratch = static_cast<uint8_t*>(v);
-      s->gscratch_bytes = need;
-    }
-    while (!rc && s->gev.size() < 2 * (size_t)j.chunks) {
-      hipEvent_t e;
-      if (step(hipEventCreate(&e))) s->gev.push_back(e);
-    }
+    if (!hip.step(hipSetDevice(s->cfg.device)) ||
+        !pack_scratch(hip, s, (size_t)j.per_chunk * (stride + 8)) || !pack_events(hip, s, j.chunks))
+      break;
     // the list stands behind the records (stride is a multiple of 16)
     uint2* const dpairs = reinterpret_cast<uint2*>(s->gscratch + (size_t)j.per_chunk * stride);
-    for (uint32_t ch = 0; ch < j.chunks && !rc; ++ch) {
+    for (uint32_t ch = 0; ch < j.chunks && !hip.rc; ++ch) {
       const size_t i0 = (size_t)ch * j.per_chunk;
       const uint32_t k = (uint32_t)std::min<size_t>(j.per_chunk, m - i0);
-      step(h2d(s, dpairs, j.pairs.data() + i0, k)) &&
-          step(hipEventRecord(s->gev[2 * ch], s->stream)) &&
-          step(rs::launch_gather(s->d, dpairs, k, Y, s->gscratch, s->stream)) &&
-          step(hipEventRecord(s->gev[2 * ch + 1], s->stream)) &&
-          step(hipMemcpyAsync(j.host + i0 * stride, s->gscratch, (size_t)k * stride,
-                              hipMemcpyDeviceToHost, s->stream));
+      hip.step(h2d(s, dpairs, j.pairs.data() + i0, k)) &&
+          hip.step(hipEventRecord(s->gev[2 * ch], s->stream)) &&
+          hip.step(rs::launch_gather(s->d, dpairs, k, Y, s->gscratch, s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * ch + 1], s->stream)) &&
+          hip.step(hipMemcpyAsync(j.host + i0 * stride, s->gscratch, (size_t)k * stride,
+                                  hipMemcpyDeviceToHost, s->stream));
     }
   }
   // every started shard is waited for, also after an error: its copies write out and the stages
@@ -1542,24 +1561,14 @@ int64_t raft_gather_read(raft_sim_t* r, const uint32_t* clusters, uint32_t n, ui
     Shard* s = r->sh[d];
     GatherJob& j = job[d];
     if (j.pairs.empty()) {
-      if (!rc) s->gather_ms = 0;
+      if (!hip.rc) s->gather_ms = 0;
       continue;
     }
-    step(hipSetDevice(s->cfg.device));
-    step(hipStreamSynchronize(s->stream));
-    if (rc) continue;
-    double ms = 0;
-    for (uint32_t ch = 0; ch < j.chunks && !rc; ++ch) {
-      float t = 0;
-      if (step(hipEventElapsedTime(&t, s->gev[2 * ch], s->gev[2 * ch + 1]))) ms += t;
-    }
-    if (rc) continue;
-    s->gather_ms = ms;
-    if (!j.stage.empty())
+    if (pack_wait(hip, s, j.chunks, &Shard::gather_ms) && !j.stage.empty())
       for (size_t i = 0; i < j.pos.size(); ++i)
         memcpy(dst + (size_t)j.pos[i] * stride, j.stage.data() + i * stride, stride);
   }
-  return rc ? rc : (int64_t)bytes;
+  return hip.rc ? hip.rc : (int64_t)bytes;
 }
 
 // Diagnostic (not part of include/raftsim.h): device time of the last raft_gather_read's kernels
@@ -1577,8 +1586,8 @@ extern "C" int raftsim_diag_gather_ms(raft_sim_t* r, double* ms) {
 // cut into chunks of the shard's scratch (the gather's, GATHER_SCRATCH_BYTES): a chunk's distinct
 // records are uploaded once each, its (local cluster, slot) list behind them, and one kernel
 // writes its targets; the chunks of a shard follow each other on its stream, all shards run at
-// once, and every started shard is waited for. The host's bookkeeping of a touched shard is what
-// the per-node writes leave, taken together.
+// once, and every started shard is waited for (pack_wait). The host's bookkeeping of a touched
+// shard is what the per-node writes leave, taken together.
 static const char* const NODE_FAULT_TEXT[] = {
     "", "role > 3", "voted_for > nodes", "leader_id > nodes", "fault > 4",
     "votes outside ids 1..nodes", "ls_keys outside the peers", "entries_is_seq > 1", "ls_present > 1", "log_len > log_cap",
@@ -1604,11 +1613,7 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
     return fail(-EINVAL, "raft_scatter_write needs the part RAFT_GATHER_%s", part_name[5]);
   char what[160];
   for (uint32_t i = 0; i < n; ++i) {
-    if (clusters[i] >= r->cfg.n_clusters) {
-      snprintf(what, sizeof what, "clusters[%u] = %u is outside the handle's %u clusters", i,
-               clusters[i], r->cfg.n_clusters);
-      return fail(-EINVAL, "%s", what);
-    }
+    if ((rc = pack_cluster_ok(r, clusters, i))) return rc;
     const uint32_t rec = records ? records[i] : i;
     if (rec >= n_records) {
       snprintf(what, sizeof what, "records[%u] = %u is outside the buffer's %u records", i, rec,
@@ -1664,11 +1669,7 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
     return fail(-EINVAL, "%s", what);
   }
 
-  auto step = [&](hipError_t e) {
-    if (!rc && e != hipSuccess) rc = fail(-EIO, "HIP error in raft_scatter_write: %s",
-                                          hipGetErrorString(e));
-    return !rc;
-  };
+  PackCall hip = {"raft_scatter_write"};
   // Per shard: its chunks [first, first + count) of the plan and the scratch the largest needs. A
   // chunk's records are staged in slot order (one host copy), unless they stand in the caller's
   // buffer as a run in that order (a pack used whole: uploaded straight from the buffer).
@@ -1681,11 +1682,11 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
   // the staging buffers live until every shard has been waited for
   std::vector<std::vector<uint8_t>> stages(plan.chunks.size());
   std::vector<size_t> started;
-  for (size_t d = 0; d < G && !rc; ++d) {
+  for (size_t d = 0; d < G && !hip.rc; ++d) {
     if (!count[d]) continue;
     Shard* s = r->sh[d];
     started.push_back(d);
-    if (!step(hipSetDevice(s->cfg.device))) break;
+    if (!hip.step(hipSetDevice(s->cfg.device))) break;
     // the bookkeeping of the per-node writes
     s->storm_until = 0;
     s->audit_valid = false;
@@ -1694,25 +1695,8 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
     size_t need = 0;
     for (size_t i = first[d]; i < first[d] + count[d]; ++i)
       need = std::max<size_t>(need, plan.chunks[i].bytes(stride));
-    if (s->gscratch_bytes < need) {
-      if (!step(hipStreamSynchronize(s->stream))) break;
-      if (s->gscratch) (void)hipFree(s->gscratch);
-      s->gscratch = nullptr;
-      s->gscratch_bytes = 0;
-      void* v = nullptr;
-      const hipError_t e = hipMalloc(&v, need);
-      if (e != hipSuccess) {
-        rc = fail(-ENOMEM, "hipMalloc failed in raft_scatter_write: %s", hipGetErrorString(e));
-        break;
-      }
-      s->gscratch = static_cast<uint8_t*>(v);
-      s->gscratch_bytes = need;
-    }
-    while (!rc && s->gev.size() < 2 * count[d]) {
-      hipEvent_t e;
-      if (step(hipEventCreate(&e))) s->gev.push_back(e);
-    }
-    for (size_t i = 0; i < count[d] && !rc; ++i) {
+    if (!pack_scratch(hip, s, need) || !pack_events(hip, s, count[d])) break;
+    for (size_t i = 0; i < count[d] && !hip.rc; ++i) {
       const rs::ScatterChunk& ch = plan.chunks[first[d] + i];
       const uint32_t* const recs = plan.records.data() + ch.rec0;
       bool run = true;                           // the records stand in the buffer as in the chunk
@@ -1727,34 +1711,23 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
       }
       // the list stands behind the records (stride is a multiple of 16)
       uint8_t* const dpairs = s->gscratch + ch.records * stride;
-      step(hipMemcpyAsync(s->gscratch, up, ch.records * stride, hipMemcpyHostToDevice,
-                          s->stream)) &&
-          step(hipMemcpyAsync(dpairs, plan.pairs.data() + ch.pair0,
-                              ch.pairs * sizeof(rs::ScatterPair), hipMemcpyHostToDevice,
+      hip.step(hipMemcpyAsync(s->gscratch, up, ch.records * stride, hipMemcpyHostToDevice,
                               s->stream)) &&
-          step(hipEventRecord(s->gev[2 * i], s->stream)) &&
-          step(rs::launch_scatter(s->d, dpairs, (uint32_t)ch.pairs, Y, s->gscratch, s->stream)) &&
-          step(hipEventRecord(s->gev[2 * i + 1], s->stream));
+          hip.step(hipMemcpyAsync(dpairs, plan.pairs.data() + ch.pair0,
+                                  ch.pairs * sizeof(rs::ScatterPair), hipMemcpyHostToDevice,
+                                  s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i], s->stream)) &&
+          hip.step(rs::launch_scatter(s->d, dpairs, (uint32_t)ch.pairs, Y, s->gscratch,
+                                      s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i + 1], s->stream));
     }
   }
   // every started shard is waited for, also after an error: its uploads read the stages
-  for (size_t d : started) {
-    Shard* s = r->sh[d];
-    step(hipSetDevice(s->cfg.device));
-    const hipError_t e = hipStreamSynchronize(s->stream);   // also when an earlier shard failed
-    step(e);
-    if (rc) continue;
-    double ms = 0;
-    for (size_t i = 0; i < count[d] && !rc; ++i) {
-      float t = 0;
-      if (step(hipEventElapsedTime(&t, s->gev[2 * i], s->gev[2 * i + 1]))) ms += t;
-    }
-    if (!rc) s->scatter_ms = ms;
-  }
-  if (!rc)
+  for (size_t d : started) pack_wait(hip, r->sh[d], count[d], &Shard::scatter_ms);
+  if (!hip.rc)
     for (size_t d = 0; d < G; ++d)
       if (!count[d]) r->sh[d]->scatter_ms = 0;
-  return rc ? rc : (int64_t)n;
+  return hip.rc ? hip.rc : (int64_t)n;
 }
 
 // Diagnostic (not part of include/raftsim.h): device time of the last raft_scatter_write's kernels

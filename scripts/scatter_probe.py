@@ -7,7 +7,8 @@
   python scripts/scatter_probe.py c4_n9   C4-N9, 1,024 x 9 at tick 110k: all 1,024 clusters
 
 Per measurement: kernel ms (raftsim_diag_scatter_ms) and wall ms around scatter(), best of the
-last three of four calls, and GB/s of pack bytes. The baseline is the loop a user writes without
+last three of four calls, and GB/s of pack bytes; the same for the gather that makes the pack
+(raftsim_diag_gather_ms). The baseline is the loop a user writes without
 the scatter for the same clusters -- restore_cluster's call sequence (set_tick, write_nodes,
 write_clusters, N x write_arena, 2N x write_queue, N x write_commit_stream) as bare ctypes calls
 on views of the pack's bytes made beforehand, so that no Python conversion is timed. One JSON line
@@ -55,6 +56,22 @@ def scatter_cost(name, sim, pack, clusters, records=None):
           "kernel_GBps": round(mb / kernel, 1), "wall_ms": round(wall, 3),
           "wall_GBps": round(mb / wall, 2)})
     return wall
+
+
+def gather_cost(name, sim, ids, parts):
+    """The gather of the same pack: kernel ms (raftsim_diag_gather_ms) and wall ms, as above."""
+    packs = []
+
+    def call():
+        packs[:] = [sim.gather(ids, parts=parts)]
+        return sim.last_gather_ms()
+
+    kernel, wall = best(call)
+    mb = len(ids) * packs[0].layout["stride"] / 1e6
+    emit({"what": name, "records": len(ids), "stride": packs[0].layout["stride"],
+          "read_MB": round(mb, 1), "kernel_ms": round(kernel, 4),
+          "kernel_GBps": round(mb / kernel, 1), "wall_ms": round(wall, 3)})
+    return packs[0]
 
 
 def write_loop(sim, pack):
@@ -105,7 +122,7 @@ def main(which):
     ids += [c for c in range(sim.C) if c not in set(ids)][:take - len(ids)]   # (fewer diverged)
     emit({"what": f"{which}: handle", "tick": sim.tick, "diverged": total, "clusters": len(ids)})
     parts = [p for p in PARTS if p != "streams" or sim.config.commit_stream_cap]
-    pack = sim.gather(ids, parts=parts)
+    pack = gather_cost(f"{which}: the gather of these {take} clusters", sim, ids, parts)
     want = sim.digest()
     wall = scatter_cost(f"{which}: {take} clusters back to their ids", sim, pack, ids)
     assert np.array_equal(sim.digest(), want)
