@@ -7,13 +7,14 @@
 #include <algorithm>
 #include <vector>
 
+#include "launch_plan.hpp"
 #include "node_codec.hpp"
 #include "scatter_host.hpp"
 #include "summary_host.hpp"
 
 namespace rs {
-hipError_t launch_tick(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st, hipEvent_t ev0,
-                       hipEvent_t ev1, bool steady, bool storm);
+hipError_t launch_tick(const DevSim& S, TickPath path, uint32_t t0, uint32_t nt, hipStream_t st,
+                       hipEvent_t ev0, hipEvent_t ev1);
 hipError_t launch_sched_key(const DevSim& S, uint32_t t0, hipStream_t st);
 hipError_t launch_sched_perm(const DevSim& S, uint32_t* zero, uint32_t* perm, uint32_t* nslots,
                              hipStream_t st);
@@ -68,58 +69,26 @@ static int unusable() {
 
 struct Shard {
   raft_sim_config_t cfg;
-  uint32_t N, Q, L, A, C, NN, tpl;
-  uint64_t tick;        // the shard's next tick
-  uint64_t ticks_run;   // ticks simulated by this handle (node_ticks counts these)
+  uint32_t N, Q, L, A, C, NN;
+  // What a tick launch is (launch_plan.hpp): fixed at create, and what changes between launches
+  rs::LaunchFixed lf;
+  rs::LaunchState ls;
   hipStream_t stream;
   hipEvent_t ev_start, ev_stop;
-  // Start/stop events in a launch's dispatch packet time the kernel alone, but measured 8.2 against
-  // 2.5 us per back-to-back launch of an empty kernel on MI355X (scripts/launch_probe.hip): a
-  // steady-path launch (~0.025 ms at C2) carries them only when it is the first after a sync
-  // (the kernel time reported is that launch's); general-kernel launches (milliseconds, and their
-  // cost changes over a run as logs grow and nodes halt) are all timed. RAFTSIM_LAUNCH_EVENTS=1
-  // times every launch (diagnostic).
-  bool launch_events;
   std::vector<uint8_t> ktimed;   // per launch since the last sync: carries an event pair
   std::vector<hipEvent_t> kev;   // per tick-kernel launch of a step: start, stop
   DevSim d;
   std::vector<void*> allocs;
   double last_ms, last_step_ms;
   uint32_t last_timed;           // launches of the last sync window that carried an event pair
-  bool pending;                  // launches enqueued since the last sync
-  uint32_t pending_launches;
+  bool pending;                  // a step has been enqueued since the last sync
   uint32_t last_launches;
   unsigned long long* client_pw;
   // RAFT_SCHED_ALIGNED: the spare histogram (the schedule kernel zeroes it while reading d.shist;
-  // the two swap every rebuild) and the wave-slot -> cluster map of the next launch. keys_written:
-  // the last tick launch wrote every cluster's key and the matching histogram into d.skey /
-  // d.shist; otherwise a rebuild zeroes d.shist and computes both from the state (sched_key).
-  // Stale keys (after host writes or set_tick) change the packing (speed), never the results; a
-  // histogram always counts each cluster once, so a packing always places each cluster once.
+  // the two swap every rebuild) and the wave-slot -> cluster map of the next launch
   uint32_t *soff, *sperm, *snslots;   // + the slot count of the packing
-  bool keys_written;
-  uint64_t resort_ctr = 0;             // tick launches since create
-  uint32_t resort_every;               // rebuild period (fixed at create)
-  // steady kernel (steady_kernel.hip): LITE launches at N <= 5 without TRACE; the two bail
-  // counters alternate between steady launches (each reports and zeroes the other)
-  bool steady_ok;
-  bool last_steady;                    // the last tick launch took the steady path
-  uint32_t* nbail2;
-  uint32_t steady_parity;
-  // Path choice per launch (speed only: both paths give the same state). RAFTSIM_STEADY=auto
-  // (default): the steady kernel unless the last catch-up launch the host has seen (bail_host,
-  // written by the GPU; a few launches stale at most) took more than 1/16 of the clusters, then
-  // the general kernel for the next STEADY_COOLDOWN launches. The first launch of a handle is
-  // steady too: the steady kernel runs init-node's election in closed form (steady_kernel.hip).
-  // "always" / "never" force a path.
-  int steady_mode;                     // 0 auto, 1 always, 2 never
-  uint32_t* bail_host;                 // host-mapped word (hipHostMalloc)
-  uint32_t steady_cooldown;
-  // Ticks before this one are storm ticks (tick_wave.hpp, STORM): the handle is fresh from
-  // init-node with client traffic, so no timer fires before el_base and the only events are
-  // client-sets at followers. Any host write of state or of the clock ends it (0).
-  uint32_t storm_until;
-  bool storm_ran = false;              // a storm-kernel launch has run (raftsim_diag_storm_bails)
+  uint32_t* nbail2;                    // the steady kernel's two bail counters (lf.steady_ok)
+  uint32_t* bail_host;                 // the bail report: a host-mapped word (hipHostMalloc)
   // The device-side queries. qev0 / qev1: the events around a query's kernels. raft_viol_read: the
   // compaction's scratch (violations_kernel.hip) and the device time of the last query
   // (raftsim_diag_viol_ms). raft_census_read / raft_census_select (census_kernel.hip): their
@@ -131,13 +100,10 @@ struct Shard {
   double census_ms;
   // raft_audit_read / raft_audit_select (audit_kernel.hip): the per-cluster records and the
   // scratch (partial and folded summaries, the compaction's counts), made by the first query, and
-  // the last query's device time (raftsim_diag_audit_ms). audit_valid: the records and the folded
-  // summary are those of the state as it stands; every call that can change a log or a commit
-  // index clears it (steps, raft_sim_write_nodes / _arena / _clusters), so queries in between
-  // walk the arenas once.
+  // the last query's device time (raftsim_diag_audit_ms). The records and the folded summary are
+  // valid while ls.audit_valid (launch_plan.hpp has the calls that clear it).
   raft_audit_record_t* arec;
   unsigned long long* ascratch;
-  bool audit_valid;
   double audit_ms;
   // raft_gather_read (gather_kernel.hip): the device scratch its records are packed into and the
   // (cluster, slot) list behind them in the same allocation, made and grown by the queries up to
@@ -152,18 +118,6 @@ struct Shard {
   // pack_events and pack_wait below serve both calls.
   double scatter_ms;
 };
-constexpr uint32_t STEADY_COOLDOWN = 2;
-// The wave packing is rebuilt every RESORT_EVERY-th tick launch and reused in between: with
-// key-pure waves a steady-state cluster keeps its wave mates' phase, so a packing stays good for
-// more than one 10k-tick launch, and skipping the schedule kernel (C2: 14.6 us) every other
-// launch measured C2 step wall 0.127 -> 0.119 ms with the tick kernel unchanged (every 4th: no
-// further gain). Results never depend on the packing.
-constexpr uint32_t RESORT_EVERY = 2;
-// LITE handles: a steady-state packing is a rotation of itself one launch later (every cluster's
-// next event moves by the same launch length), so it is rebuilt every 8th launch
-constexpr uint32_t RESORT_EVERY_LITE = 8;
-// clusters per handle from which storm ticks run the storm kernel (raft_sim_create has the numbers)
-constexpr uint32_t STORM_MIN_CLUSTERS = 131072;
 
 // Exported functions take their C linkage from the declarations in include/raftsim.h.
 
@@ -243,22 +197,30 @@ static void sh_destroy(Shard* s) {
   delete s;
 }
 
-// One shard: cfg holds its own cluster count, global offset and device (validated by the caller).
-static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
-  int rc = 0;
-  HIP_OK(hipSetDevice(cfg->device));
-  hipDeviceProp_t prop;
-  HIP_OK(hipGetDeviceProperties(&prop, cfg->device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(-EIO, "device is %s; libraftsim.so is built for gfx950", prop.gcnArchName);
-  HIP_OK(rs::configure_kernels());
+// What raft_sim_create reads from the environment for the launch plan.
+static rs::LaunchEnv launch_env() {
+  rs::LaunchEnv env = {rs::STEADY_AUTO, false, rs::STORM_MIN_CLUSTERS};
+  const char* m = getenv("RAFTSIM_STEADY");
+  if (m && !strcmp(m, "always")) env.steady_mode = rs::STEADY_ALWAYS;
+  if (m && !strcmp(m, "never")) env.steady_mode = rs::STEADY_NEVER;
+  const char* le = getenv("RAFTSIM_LAUNCH_EVENTS");
+  env.launch_events = le && !strcmp(le, "1");
+#ifdef RS_DIAG_BUILD   // scripts/storm_probe.py forces either path; the product takes no override
+  if (const char* sm = getenv("RAFTSIM_STORM_MIN_CLUSTERS"))
+    env.storm_min_clusters = (uint32_t)strtoul(sm, nullptr, 10);
+#endif
+  return env;
+}
 
-  Shard* s = new Shard();
+// Everything of sh_create that can fail once the shard exists: the caller destroys it on failure.
+static int sh_init(Shard* s, const raft_sim_config_t* cfg) {
+  int rc = 0;
   s->cfg = *cfg;
   s->N = cfg->nodes; s->Q = cfg->inbox_cap; s->L = cfg->log_cap; s->C = cfg->n_clusters;
   s->A = cfg->arena_cap ? cfg->arena_cap : 4 * cfg->log_cap;
   s->NN = s->C * s->N;
-  s->tpl = cfg->ticks_per_launch ? std::min<uint32_t>(cfg->ticks_per_launch, 65536u) : 10000u;
+  s->lf = rs::launch_fixed(*cfg, launch_env());
+  s->ls = rs::launch_state(*cfg);
   DevSim& d = s->d;
   d.C = s->C; d.N = s->N; d.Q = s->Q; d.L = s->L; d.A = s->A; d.NN = s->NN;
   d.goff = cfg->cluster_offset;
@@ -278,8 +240,7 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
   uint64_t pw[32];
   rs::client_powers(cfg->client_ppm, pw);
   d.client_pw = nullptr;
-  d.lite = cfg->client_ppm == 0 && cfg->drop_ppm == 0 && cfg->dup_ppm == 0 && cfg->part_ppm == 0 &&
-           cfg->dmin == cfg->dmax;
+  d.lite = s->ls.lite;   // no kernel reads it and the host reads ls.lite: it keeps this value
   d.client_top = -1;
   for (int i = 0; i < 32; ++i)
     if (pw[i]) d.client_top = i;
@@ -297,70 +258,34 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
       (rc = dalloc(s, &d.tent, NN * std::max<uint32_t>(d.TE, 1))) ||
       (rc = dalloc(s, &d.tecount, NN)) ||
       (rc = dalloc(s, &d.viol, (size_t)s->C * 4)) ||
-      (rc = dalloc(s, &s->vscratch, rs::viol_scratch_words(s->C)))) {
-    sh_destroy(s);
+      (rc = dalloc(s, &s->vscratch, rs::viol_scratch_words(s->C))))
     return rc;
-  }
   d.client_pw = s->client_pw;
   d.wavelog = nullptr;
 #ifdef RS_WAVELOG
-  if ((rc = dalloc(s, &d.wavelog, (size_t)rs::sched_slots_bound(s->C, s->N) * 12))) {
-    sh_destroy(s);
-    return rc;
-  }
+  if ((rc = dalloc(s, &d.wavelog, (size_t)rs::sched_slots_bound(s->C, s->N) * 12))) return rc;
 #endif
-  s->steady_ok = d.lite && s->N <= 5 && !d.TC && !(cfg->variant_flags & RAFT_VARIANT_SPEC);
-  // init-node's deadlines are el_base or more ahead and every re-arm is too (SIM_SPEC D4; the
-  // Spec-Raft control re-arms on fewer events): until el_base, client-sets are the only events
-  s->storm_until = cfg->client_ppm && !d.TC ? cfg->el_base : 0u;
-  s->resort_every = d.lite ? RESORT_EVERY_LITE : RESORT_EVERY;
-  {
-    const char* le = getenv("RAFTSIM_LAUNCH_EVENTS");
-    s->launch_events = le && !strcmp(le, "1");
-  }
-  if (s->steady_ok && (rc = dalloc(s, &s->nbail2, 2))) {
-    sh_destroy(s);
+  if (s->lf.steady_ok && (rc = dalloc(s, &s->nbail2, 2))) return rc;
+  // the storm kernel's leftover list (storm_kernel.hip)
+  if (s->lf.storm_kernel &&
+      ((rc = dalloc(s, &d.storm_list, s->C)) || (rc = dalloc(s, &d.storm_count, 1))))
     return rc;
-  }
-  // the storm kernel's leftover list (storm_kernel.hip), while storm ticks lie ahead. One lane per
-  // cluster needs clusters enough to fill the chip (two 64-cluster waves per SIMD at least: at
-  // C4's 16,384 clusters its 256 waves ran 36 ms against the lane-per-node body's 14): below that
-  // the storm ticks run the general STORM body.
-  // (Its registers hold arrivals below 2^28 and hop counts below 16.)
-  uint32_t storm_min = STORM_MIN_CLUSTERS;
-#ifdef RS_DIAG_BUILD   // scripts/storm_probe.py forces either path; the product takes no override
-  if (const char* sm = getenv("RAFTSIM_STORM_MIN_CLUSTERS")) storm_min = (uint32_t)strtoul(sm, nullptr, 10);
-#endif
-  if (s->storm_until && s->C >= storm_min && cfg->el_base < (1u << 28) && cfg->client_redirects < 16 &&
-      ((rc = dalloc(s, &s->d.storm_list, s->C)) ||
-                         (rc = dalloc(s, &s->d.storm_count, 1)))) {
-    sh_destroy(s);
-    return rc;
-  }
-  if (s->steady_ok) {
-    const char* m = getenv("RAFTSIM_STEADY");
-    s->steady_mode = m && !strcmp(m, "always") ? 1 : m && !strcmp(m, "never") ? 2 : 0;
-
-    s->steady_cooldown = 0;
+  if (s->lf.steady_ok) {
     void* hp = nullptr;
     if (hipHostMalloc(&hp, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer(reinterpret_cast<void**>(&d.bail_report), hp, 0) != hipSuccess) {
       if (hp) (void)hipHostFree(hp);
-      sh_destroy(s);
       return fail(-ENOMEM, "hipHostMalloc (bail report) failed");
     }
     s->bail_host = static_cast<uint32_t*>(hp);
     *s->bail_host = 0;
   }
-  if (cfg->schedule == RAFT_SCHED_ALIGNED) {
-    if ((rc = dalloc(s, &d.skey, s->C)) || (rc = dalloc(s, &d.shist, rs::SCHED_BUCKETS)) ||
-        (rc = dalloc(s, &s->soff, rs::SCHED_BUCKETS)) ||
-        (rc = dalloc(s, &s->sperm, rs::sched_slots_bound(s->C, s->N))) ||
-        (rc = dalloc(s, &s->snslots, 1))) {
-      sh_destroy(s);
-      return rc;
-    }
-  }
+  if (s->lf.aligned &&
+      ((rc = dalloc(s, &d.skey, s->C)) || (rc = dalloc(s, &d.shist, rs::SCHED_BUCKETS)) ||
+       (rc = dalloc(s, &s->soff, rs::SCHED_BUCKETS)) ||
+       (rc = dalloc(s, &s->sperm, rs::sched_slots_bound(s->C, s->N))) ||
+       (rc = dalloc(s, &s->snslots, 1))))
+    return rc;
   hipError_t e;
   if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&s->ev_start)) != hipSuccess ||
@@ -383,85 +308,59 @@ static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
           hipSuccess ||
       (e = rs::launch_init(d, s->stream)) != hipSuccess ||
       (e = rs::launch_viol_clear(d, s->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(s->stream)) != hipSuccess) {
-    sh_destroy(s);
+      (e = hipStreamSynchronize(s->stream)) != hipSuccess)
     return fail(-EIO, "HIP error during create: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// One shard: cfg holds its own cluster count, global offset and device (validated by the caller).
+static int sh_create(const raft_sim_config_t* cfg, Shard** out) {
+  HIP_OK(hipSetDevice(cfg->device));
+  hipDeviceProp_t prop;
+  HIP_OK(hipGetDeviceProperties(&prop, cfg->device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(-EIO, "device is %s; libraftsim.so is built for gfx950", prop.gcnArchName);
+  HIP_OK(rs::configure_kernels());
+  Shard* s = new Shard();
+  const int rc = sh_init(s, cfg);
+  if (rc) {
+    sh_destroy(s);
+    return rc;
   }
   *out = s;
   return 0;
 }
 
-// Enqueue n_ticks on the shard's stream. s->tick advances launch by launch, so after a failure it
-// still names the tick the state has reached (the handle is then poisoned anyway).
+// Enqueue n_ticks on the shard's stream, launch by launch as rs::plan_launch says. ls.tick
+// advances with every enqueued launch, so after a failure it still names the tick the state has
+// reached (the handle is then poisoned anyway).
 static int sh_step_async(Shard* s, uint32_t n_ticks) {
-  s->audit_valid = false;
+  rs::invalidate(s->ls, rs::ON_STEP);
   HIP_OK(hipSetDevice(s->cfg.device));
-  uint32_t launches = s->pending_launches;
   if (!s->pending) {
     HIP_OK(hipEventRecord(s->ev_start, s->stream));
-    launches = 0;
     s->pending = true;
   }
   for (uint32_t done = 0; done < n_ticks;) {
-    uint32_t nt = std::min(s->tpl, n_ticks - done);
-    const uint32_t t0 = (uint32_t)s->tick;
-    // storm ticks run alone in a launch of their own (the STORM body)
-    const bool storm = t0 < s->storm_until;
-    if (storm) nt = std::min(nt, s->storm_until - t0);
-    // Path (speed only: both paths give the same state). Host writes may have cleared lite.
-    bool steady = s->steady_ok && s->d.lite;
-    if (steady && s->steady_mode == 2) steady = false;
-    if (steady && s->steady_mode == 0) {
-      if (s->steady_cooldown) {
-        --s->steady_cooldown;
-        steady = false;
-      } else if (__atomic_load_n(s->bail_host, __ATOMIC_RELAXED) > s->C / 16) {
-        __atomic_store_n(s->bail_host, 0u, __ATOMIC_RELAXED);
-        s->steady_cooldown = STEADY_COOLDOWN - 1;
-        steady = false;
+    const uint32_t launch = s->ls.window_launch;
+    const rs::LaunchPlan p = rs::plan_launch(
+        s->lf, s->ls, n_ticks - done,
+        s->bail_host ? __atomic_load_n(s->bail_host, __ATOMIC_RELAXED) : 0u);
+    if (p.reset_report) __atomic_store_n(s->bail_host, 0u, __ATOMIC_RELAXED);
+    if (p.sched != rs::SCHED_NONE) {
+      if (p.sched == rs::SCHED_KEY_PERM) {
+        HIP_OK(hipMemsetAsync(s->d.shist, 0, rs::SCHED_BUCKETS * 4, s->stream));
+        HIP_OK(rs::launch_sched_key(s->d, p.t0, s->stream));
       }
+      HIP_OK(rs::launch_sched_perm(s->d, s->soff, s->sperm, s->snslots, s->stream));
+      // the schedule kernel read d.shist and zeroed soff: the next key-writing launch fills it
+      std::swap(s->d.shist, s->soff);
+      s->d.perm = s->sperm;
+      s->d.nslots = s->snslots;
     }
-    bool no_keys = false;                // this launch writes no packing keys
-    bool no_perm = false;
-    if (steady) {
-      // the steady kernel runs the clusters in id order: no packing, no keys. (Packed by next
-      // event, 64 to a wave, the same launch took 0.0329 against 0.0318 ms: a lane runs its own
-      // cluster's clock, and the packing's perm load sat in front of every state load.)
-      no_perm = no_keys = true;
-      s->keys_written = false;
-    } else if (s->cfg.schedule == RAFT_SCHED_ALIGNED && s->resort_ctr == 0 && !s->d.client_ppm) {
-      // The handle's first launch without client traffic (every cluster from init-node or as the
-      // host wrote it): clusters in id order. Per-cluster clocks make a wave's trips its busiest
-      // cluster's event ticks whatever its mates are, and the packing's key and sort kernels
-      // measured +35-40 us on the 100-us first launch of 65,536 clusters (scripts/init_probe.py).
-      // Keys are not written: the next launch's rebuild computes them from the state.
-      no_perm = no_keys = true;
-      s->keys_written = false;
-      ++s->resort_ctr;
-    } else if (s->cfg.schedule == RAFT_SCHED_ALIGNED) {
-      // pack clusters with the same next event onto the same waves for this launch: keys and
-      // histogram come from the previous tick launch, or are computed from the state. The
-      // packing is rebuilt every resort_every-th launch and reused in between (any packing gives
-      // the same results); only the launch before a rebuild writes keys.
-      if (s->resort_ctr % s->resort_every == 0) {
-        if (!s->keys_written) {
-          HIP_OK(hipMemsetAsync(s->d.shist, 0, rs::SCHED_BUCKETS * 4, s->stream));
-          HIP_OK(rs::launch_sched_key(s->d, t0, s->stream));
-        }
-        HIP_OK(rs::launch_sched_perm(s->d, s->soff, s->sperm, s->snslots, s->stream));
-        // the schedule kernel read d.shist and zeroed soff: the next key-writing launch fills it
-        std::swap(s->d.shist, s->soff);
-        s->d.perm = s->sperm;
-        s->d.nslots = s->snslots;
-      }
-      ++s->resort_ctr;
-      s->keys_written = s->resort_ctr % s->resort_every == 0;   // the next launch rebuilds
-      no_keys = !s->keys_written;
-    }
-    const bool timed = s->launch_events || launches == 0 || !steady;
-    if (s->ktimed.size() < launches + 1) s->ktimed.resize(launches + 1);
-    s->ktimed[launches] = timed;
-    while (timed && s->kev.size() < 2 * (size_t)(launches + 1)) {
+    if (s->ktimed.size() < launch + 1) s->ktimed.resize(launch + 1);
+    s->ktimed[launch] = p.timed;
+    while (p.timed && s->kev.size() < 2 * (size_t)(launch + 1)) {
       hipEvent_t e;   // timing only: no system-scope fence (cache writeback) per launch
       HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
       s->kev.push_back(e);
@@ -470,24 +369,18 @@ static int sh_step_async(Shard* s, uint32_t n_ticks) {
     HIP_OK(hipMemsetAsync(s->d.wavelog, 0,
                           (size_t)rs::sched_slots_bound(s->C, s->N) * 192 / (64 / s->N), s->stream));
 #endif
-    s->last_steady = steady;
-    if (storm && !steady && s->d.storm_list && !s->d.TC && !s->d.lite) s->storm_ran = true;
-    if (steady) {
-      s->d.nbail = s->nbail2 + s->steady_parity;
-      s->d.nbail_zero = s->nbail2 + (s->steady_parity ^ 1);
-      s->steady_parity ^= 1;
+    if (p.path == rs::PATH_STEADY) {
+      s->d.nbail = s->nbail2 + p.bail_parity;
+      s->d.nbail_zero = s->nbail2 + (p.bail_parity ^ 1);
     }
     DevSim D = s->d;
-    if (no_perm) D.perm = nullptr;
-    if (no_keys) D.shist = nullptr;
-    HIP_OK(rs::launch_tick(D, t0, nt, s->stream,
-                           timed ? s->kev[2 * launches] : nullptr,
-                           timed ? s->kev[2 * launches + 1] : nullptr, steady, storm && !steady));
-    done += nt;
-    s->tick += nt;
-    s->ticks_run += nt;
-    ++launches;
-    s->pending_launches = launches;
+    if (!p.use_perm) D.perm = nullptr;
+    if (!p.write_keys) D.shist = nullptr;
+    HIP_OK(rs::launch_tick(D, p.path, p.t0, p.nt, s->stream,
+                           p.timed ? s->kev[2 * launch] : nullptr,
+                           p.timed ? s->kev[2 * launch + 1] : nullptr));
+    rs::launch_enqueued(s->ls, p);
+    done += p.nt;
   }
   return 0;
 }
@@ -499,9 +392,9 @@ static int sh_sync(Shard* s) {
     HIP_OK(hipStreamSynchronize(s->stream));
     return 0;
   }
-  const uint32_t launches = s->pending_launches;
+  const uint32_t launches = s->ls.window_launch;
   s->pending = false;
-  s->pending_launches = 0;
+  rs::synced(s->ls);
   HIP_OK(hipEventRecord(s->ev_stop, s->stream));
   HIP_OK(hipEventSynchronize(s->ev_stop));
   float ms = 0, kms = 0;
@@ -584,8 +477,7 @@ static int sh_read_nodes(Shard* s, uint32_t c0, uint32_t nc, raft_node_t* out) {
 static int sh_write_nodes(Shard* s, uint32_t c0, uint32_t nc, const raft_node_t* in) {
   int rc = check_range(s, c0, nc);
   if (rc) return rc;
-  s->storm_until = 0;
-  s->audit_valid = false;
+  rs::invalidate(s->ls, rs::ON_WRITE_NODES);
   if (!in) return fail(-EINVAL, "null input");
   HIP_OK(hipSetDevice(s->cfg.device));
   const uint32_t N = s->N;
@@ -636,15 +528,14 @@ static int sh_read_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t which
 static int sh_write_queue(Shard* s, uint32_t cluster, uint32_t id, uint32_t which,
                          const raft_msg_t* in, uint32_t count) {
   int rc = check_node(s, cluster, id);
-  if (!rc) s->storm_until = 0;
   if (rc) return rc;
+  rs::invalidate(s->ls, rs::ON_WRITE_QUEUE);
   switch (rs::queue_fault(in, count, which, id, s->N, s->Q)) {
     case rs::QUEUE_OK: break;
     case rs::QUEUE_COUNT: return fail(-EINVAL, "bad queue or count");
     default: return fail(-EINVAL, "invalid message or order");
   }
-  // a queued client-set needs the general kernel (LITE)
-  if (rs::queue_has_client_set(in, count)) s->d.lite = 0;
+  if (rs::queue_has_client_set(in, count)) rs::invalidate(s->ls, rs::ON_QUEUED_CLIENT_SET);
   HIP_OK(hipSetDevice(s->cfg.device));
   const uint32_t gi = cluster * s->N + id - 1;
   std::vector<raft_msg_t> slots(s->Q);
@@ -687,9 +578,8 @@ static int sh_read_arena(Shard* s, uint32_t cluster, uint32_t id, raft_entry_t* 
 static int sh_write_arena(Shard* s, uint32_t cluster, uint32_t id, const raft_entry_t* in,
                          uint32_t count) {
   int rc = check_node(s, cluster, id);
-  if (!rc) s->storm_until = 0;
   if (rc) return rc;
-  s->audit_valid = false;
+  rs::invalidate(s->ls, rs::ON_WRITE_ARENA);
   if (count > s->A || (count && !in)) return fail(-EINVAL, "count > arena_cap");
   HIP_OK(hipSetDevice(s->cfg.device));
   std::vector<raft_entry_t> buf(s->A);
@@ -722,8 +612,8 @@ static int sh_read_commit_stream(Shard* s, uint32_t cluster, uint32_t id, uint32
 static int sh_write_commit_stream(Shard* s, uint32_t cluster, uint32_t id, const uint32_t* in,
                                  uint32_t count) {
   int rc = check_node(s, cluster, id);
-  if (!rc) s->storm_until = 0;
   if (rc) return rc;
+  rs::invalidate(s->ls, rs::ON_WRITE_COMMIT_STREAM);
   HIP_OK(hipSetDevice(s->cfg.device));
   const uint32_t SC = s->cfg.commit_stream_cap;
   const size_t gi = (size_t)cluster * s->N + id - 1;
@@ -803,13 +693,12 @@ static int sh_read_clusters(Shard* s, uint32_t c0, uint32_t nc, raft_cluster_t* 
 static int sh_write_clusters(Shard* s, uint32_t c0, uint32_t nc, const raft_cluster_t* in) {
   int rc = check_range(s, c0, nc);
   if (rc) return rc;
-  s->storm_until = 0;
-  s->audit_valid = false;
+  rs::invalidate(s->ls, rs::ON_WRITE_CLUSTERS);
   HIP_OK(hipSetDevice(s->cfg.device));
   std::vector<raft_cluster_t> buf(in, in + nc);
   for (auto& h : buf) {
     h.reserved[0] = h.reserved[1] = h.reserved[2] = 0;
-    if (h.client_next != 0xFFFFFFFFu) s->d.lite = 0;   // a client-set is due: P0 is needed
+    if (h.client_next != 0xFFFFFFFFu) rs::invalidate(s->ls, rs::ON_CLIENT_CURSOR);
   }
   if (nc)
     HIP_OK(hipMemcpy2DAsync(cl_words(s, c0), (size_t)s->d.HB * 4, buf.data(),
@@ -834,7 +723,7 @@ static int sh_read_counters(Shard* s, raft_counters_t* out) {
     out->first_violation_tick = std::min<uint64_t>(out->first_violation_tick, b[RAFT_CTR_COUNT]);
     out->payload_max = std::max<uint64_t>(out->payload_max, b[RAFT_CTR_COUNT + 1]);
   }
-  out->node_ticks = (uint64_t)s->NN * s->ticks_run;
+  out->node_ticks = (uint64_t)s->NN * s->ls.ticks_run;
   return 0;
 }
 
@@ -960,11 +849,7 @@ int raft_sim_set_tick(raft_sim_t* r, uint64_t tick) {
   for (Shard* s : r->sh) {
     const int rc = sh_sync(s);
     if (rc) return rc;
-    s->tick = tick;
-    s->storm_until = 0;
-    // the packing keys are relative to the next launch's first tick: the next rebuild computes
-    // them from the state
-    s->keys_written = false;
+    rs::set_tick(s->ls, tick);
   }
   r->tick = tick;
   return 0;
@@ -1311,8 +1196,8 @@ extern "C" int raftsim_diag_census_ms(raft_sim_t* r, double* ms) {
 // Log audit (include/raftsim.h, "no reference counterpart, none in the oracle"): a read-only pass
 // over the hot blocks and the arenas on every shard's stream at once, behind whatever the shard
 // has enqueued. It leaves one record per cluster and the shard's summary on the device, valid
-// until the next call that can change a log or a commit index (Shard::audit_valid): the summary
-// is copied from there and folded over the shards on the host, selections compact the records
+// until the next call that can change a log or a commit index (LaunchState::audit_valid): the
+// summary is copied from there and folded over the shards on the host, selections compact the records
 // through sharded_query. Like the census it touches neither the state nor the host's bookkeeping
 // of it.
 static int audit_prepare(Shard* s) {
@@ -1323,13 +1208,13 @@ static int audit_prepare(Shard* s) {
 }
 // Enqueue the pass unless the shard's records are those of the state as it stands.
 static hipError_t audit_refresh(Shard* s) {
-  if (s->audit_valid) return hipSuccess;
+  if (s->ls.audit_valid) return hipSuccess;
   // the pass's lanes per cluster (audit_kernel.hip; DESIGN.md has both widths' figures): 64 unless
   // RAFTSIM_AUDIT_WIDTH=16 is in the environment. Same records and summary either way.
   const char* aw = getenv("RAFTSIM_AUDIT_WIDTH");
   const uint32_t width = aw && !strcmp(aw, "16") ? 16u : 64u;
   const hipError_t e = rs::launch_audit(s->d, width, s->arec, s->ascratch, s->stream);
-  s->audit_valid = e == hipSuccess;
+  s->ls.audit_valid = e == hipSuccess;
   return e;
 }
 
@@ -1339,7 +1224,7 @@ int raft_audit_read(raft_sim_t* r, raft_audit_t* out) {
   return sharded_summary(
       r, out, "raft_audit_read", audit_prepare, audit_refresh,
       [](Shard* s) { return s->ascratch + rs::audit_layout(s->C).result(); },
-      &Shard::audit_ms, [](Shard* s) { s->audit_valid = false; });
+      &Shard::audit_ms, [](Shard* s) { s->ls.audit_valid = false; });
 }
 
 int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, uint32_t none_mask,
@@ -1362,7 +1247,7 @@ int64_t raft_audit_select(raft_sim_t* r, uint32_t any_mask, uint32_t all_mask, u
       },
       &Shard::audit_ms);
   if (n < 0)
-    for (Shard* s : r->sh) s->audit_valid = false;
+    for (Shard* s : r->sh) s->ls.audit_valid = false;
   return n;
 }
 
@@ -1687,11 +1572,8 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
     Shard* s = r->sh[d];
     started.push_back(d);
     if (!hip.step(hipSetDevice(s->cfg.device))) break;
-    // the bookkeeping of the per-node writes
-    s->storm_until = 0;
-    s->audit_valid = false;
-    s->keys_written = false;
-    if (general[d]) s->d.lite = 0;
+    rs::invalidate(s->ls, rs::ON_SCATTER);
+    if (general[d]) rs::invalidate(s->ls, rs::ON_SCATTER_GENERAL);
     size_t need = 0;
     for (size_t i = first[d]; i < first[d] + count[d]; ++i)
       need = std::max<size_t>(need, plan.chunks[i].bytes(stride));
@@ -1768,11 +1650,11 @@ extern "C" int raftsim_diag_last_bails(raft_sim_t* r) {
   if (!r) return fail(-EINVAL, "null sim");
   int total = 0;
   for (Shard* s : r->sh) {
-    if (!s->steady_ok || !s->last_steady) return -1;
+    if (s->ls.last_path != rs::PATH_STEADY) return -1;
     uint32_t v = 0;
     HIP_OK(hipSetDevice(s->cfg.device));
     HIP_OK(hipStreamSynchronize(s->stream));
-    HIP_OK(hipMemcpy(&v, s->nbail2 + (s->steady_parity ^ 1), 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&v, s->nbail2 + (s->ls.steady_parity ^ 1), 4, hipMemcpyDeviceToHost));
     total += (int)v;
   }
   return total;
@@ -1786,7 +1668,7 @@ extern "C" int raftsim_diag_storm_bails(raft_sim_t* r) {
   int total = 0;
   bool any = false;
   for (Shard* s : r->sh) {
-    if (!s->storm_ran) continue;
+    if (!s->ls.storm_kernel_ran) continue;
     any = true;
     uint32_t v = 0;
     HIP_OK(hipSetDevice(s->cfg.device));

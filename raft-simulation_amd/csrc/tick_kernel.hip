@@ -3,9 +3,28 @@
 // tick_wave (tick_wave.hpp).
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
+#include "launch_plan.hpp"
 #include "tick_wave.hpp"
 
 namespace rs {
+
+// fn(std::integral_constant<int, N>) for a handle's N; there is no kernel for any other.
+template <class F>
+hipError_t with_nodes(uint32_t N, F fn) {
+  switch (N) {
+    case 2: return fn(std::integral_constant<int, 2>());
+    case 3: return fn(std::integral_constant<int, 3>());
+    case 4: return fn(std::integral_constant<int, 4>());
+    case 5: return fn(std::integral_constant<int, 5>());
+    case 6: return fn(std::integral_constant<int, 6>());
+    case 7: return fn(std::integral_constant<int, 7>());
+    case 8: return fn(std::integral_constant<int, 8>());
+    case 9: return fn(std::integral_constant<int, 9>());
+    default: return hipErrorInvalidValue;
+  }
+}
 
 // The general tick kernel: one wave per workgroup (wave lifetimes differ by up to 2x under load,
 // and a multi-wave workgroup holds its CU slot and LDS until its slowest wave ends; measured:
@@ -197,17 +216,11 @@ hipError_t launch_sched_key(const DevSim& S, uint32_t t0, hipStream_t st) {
 
 hipError_t launch_sched_perm(const DevSim& S, uint32_t* zero, uint32_t* perm, uint32_t* nslots,
                              hipStream_t st) {
-  switch (64 / S.N) {
-#define RS_PLAN(CPW)                                                                             \
-  case CPW:                                                                                      \
-    hipLaunchKernelGGL(sched_range_kernel<CPW>, dim3(SCHED_RANGE_BLOCKS), dim3(1024), 0, st, S,  \
-                       zero, perm, nslots);                                                      \
-    break;
-    RS_PLAN(32) RS_PLAN(21) RS_PLAN(16) RS_PLAN(12) RS_PLAN(10) RS_PLAN(9) RS_PLAN(8) RS_PLAN(7)
-#undef RS_PLAN
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_nodes(S.N, [&](auto n) {
+    hipLaunchKernelGGL(sched_range_kernel<64 / n()>, dim3(SCHED_RANGE_BLOCKS), dim3(1024), 0, st,
+                       S, zero, perm, nslots);
+    return hipGetLastError();
+  });
 }
 
 // Initial state: init-node (core.clj:31-38) and an empty log (log.clj:33-34) for every node.
@@ -326,68 +339,46 @@ hipError_t launch_storm_body_ns(const DevSim& S, uint32_t t0, uint32_t nt, hipSt
 hipError_t launch_storm_body(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st,
                              hipEvent_t ev0, hipEvent_t ev1) {
   const bool spec = S.variant & RAFT_VARIANT_SPEC;
-  switch (S.N) {
-#define RS_SB(NN)                                                                            \
-  case NN:                                                                                   \
-    return spec ? launch_storm_body_ns<NN, true>(S, t0, nt, st, ev0, ev1)                    \
-                : launch_storm_body_ns<NN, false>(S, t0, nt, st, ev0, ev1);
-    RS_SB(2) RS_SB(3) RS_SB(4) RS_SB(5) RS_SB(6) RS_SB(7) RS_SB(8) RS_SB(9)
-#undef RS_SB
-    default: return hipErrorInvalidValue;
-  }
+  return with_nodes(S.N, [&](auto n) {
+    return spec ? launch_storm_body_ns<n(), true>(S, t0, nt, st, ev0, ev1)
+                : launch_storm_body_ns<n(), false>(S, t0, nt, st, ev0, ev1);
+  });
 }
 
 template <int N, bool SPEC>
-hipError_t launch_tick_ns(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st, hipEvent_t ev0,
-                    hipEvent_t ev1, bool steady, bool storm) {
+hipError_t launch_tick_ns(const DevSim& S, TickPath path, uint32_t t0, uint32_t nt, hipStream_t st,
+                          hipEvent_t ev0, hipEvent_t ev1) {
+  if (!path_exists(N, SPEC, path)) return hipErrorInvalidValue;
   constexpr int CPW = 64 / N;
   constexpr size_t lds = block_lds_bytes<N, SPEC>();
   const uint32_t waves = S.perm ? sched_slots_bound(S.C, N) / CPW : (S.C + CPW - 1) / CPW;
-  if constexpr (N <= 5 && !SPEC) {
+  const auto run = [&](auto kernel, size_t lds_bytes) {
+    hipExtLaunchKernelGGL(kernel, dim3(waves), dim3(64), lds_bytes, st, ev0, ev1, 0, S, t0, nt);
+    return hipGetLastError();
+  };
+  switch (path) {
     // the steady kernel, whose workgroups run the clusters they bail through tick_wave
-    if (steady) return launch_steady(S, t0, nt, st, ev0, ev1);
+    case PATH_STEADY: return launch_steady(S, t0, nt, st, ev0, ev1);
+    case PATH_STORM_KERNEL: return launch_storm(S, t0, nt, st, ev0, ev1);
+    case PATH_STORM_BODY:
+      return run(tick_kernel<N, false, SPEC, false, true>, block_lds_bytes<N, SPEC, true>());
+    case PATH_TRACE: return run(tick_kernel<N, true, SPEC, false>, lds);
+    case PATH_LITE: return run(tick_kernel<N, false, false, true>, lds);
+    case PATH_GENERAL: return run(tick_kernel<N, false, SPEC, false>, lds);
+    case PATH_NONE: break;
   }
-  if (storm && !S.TC && !S.lite && S.storm_list)
-    return launch_storm(S, t0, nt, st, ev0, ev1);
-  if (storm && !S.TC && !S.lite)
-    hipExtLaunchKernelGGL((tick_kernel<N, false, SPEC, false, true>), dim3(waves), dim3(64),
-                          block_lds_bytes<N, SPEC, true>(), st, ev0, ev1, 0, S, t0, nt);
-  else if (S.TC)
-    hipExtLaunchKernelGGL((tick_kernel<N, true, SPEC, false>), dim3(waves), dim3(64), lds, st, ev0,
-                          ev1, 0, S, t0, nt);
-  else if (!SPEC && S.lite)
-    hipExtLaunchKernelGGL((tick_kernel<N, false, false, true>), dim3(waves), dim3(64), lds, st, ev0,
-                          ev1, 0, S, t0, nt);
-  else
-    hipExtLaunchKernelGGL((tick_kernel<N, false, SPEC, false>), dim3(waves), dim3(64), lds, st,
-                          ev0, ev1, 0, S, t0, nt);
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
-template <int N>
-hipError_t launch_tick_n(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st,
-                         hipEvent_t ev0, hipEvent_t ev1, bool steady, bool storm) {
-  if (S.variant & RAFT_VARIANT_SPEC)
-    return launch_tick_ns<N, true>(S, t0, nt, st, ev0, ev1, false, storm);
-  return launch_tick_ns<N, false>(S, t0, nt, st, ev0, ev1, steady, storm);
-}
-
-// steady: a LITE launch at N <= 5 without TRACE runs the steady kernel; storm: a launch before any
-// timer can fire in a handle fresh from init-node runs the STORM body (tick_wave.hpp). The caller
-// decides; results are the same either way.
-hipError_t launch_tick(const DevSim& S, uint32_t t0, uint32_t nt, hipStream_t st, hipEvent_t ev0,
-                       hipEvent_t ev1, bool steady, bool storm) {
-  switch (S.N) {
-    case 2: return launch_tick_n<2>(S, t0, nt, st, ev0, ev1, steady, storm);
-    case 3: return launch_tick_n<3>(S, t0, nt, st, ev0, ev1, steady, storm);
-    case 4: return launch_tick_n<4>(S, t0, nt, st, ev0, ev1, steady, storm);
-    case 5: return launch_tick_n<5>(S, t0, nt, st, ev0, ev1, steady, storm);
-    case 6: return launch_tick_n<6>(S, t0, nt, st, ev0, ev1, false, storm);
-    case 7: return launch_tick_n<7>(S, t0, nt, st, ev0, ev1, false, storm);
-    case 8: return launch_tick_n<8>(S, t0, nt, st, ev0, ev1, false, storm);
-    case 9: return launch_tick_n<9>(S, t0, nt, st, ev0, ev1, false, storm);
-    default: return hipErrorInvalidValue;
-  }
+// The launch of the kernel the host's plan names (launch_plan.hpp); results are the same whichever
+// path a launch takes. A (N, SPEC, path) without a kernel is refused (path_exists).
+hipError_t launch_tick(const DevSim& S, TickPath path, uint32_t t0, uint32_t nt, hipStream_t st,
+                       hipEvent_t ev0, hipEvent_t ev1) {
+  const bool spec = S.variant & RAFT_VARIANT_SPEC;
+  return with_nodes(S.N, [&](auto n) {
+    return spec ? launch_tick_ns<n(), true>(S, path, t0, nt, st, ev0, ev1)
+                : launch_tick_ns<n(), false>(S, path, t0, nt, st, ev0, ev1);
+  });
 }
 
 template <int N, bool TRACE, bool SPEC, bool LITE = false, bool STORM = false>
@@ -412,12 +403,9 @@ hipError_t configure_n() {
 hipError_t configure_steady();
 
 hipError_t configure_kernels() {
-  hipError_t e = hipSuccess;
-  if ((e = configure_n<2>()) || (e = configure_n<3>()) || (e = configure_n<4>()) ||
-      (e = configure_n<5>()) || (e = configure_n<6>()) || (e = configure_n<7>()) ||
-      (e = configure_n<8>()) || (e = configure_n<9>()) || (e = configure_steady()))
-    return e;
-  return hipSuccess;
+  for (uint32_t N = 2; N <= RAFT_MAX_NODES; ++N)
+    if (hipError_t e = with_nodes(N, [](auto n) { return configure_n<n()>(); })) return e;
+  return configure_steady();
 }
 
 
