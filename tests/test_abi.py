@@ -3,15 +3,13 @@ import ctypes
 import os
 import re
 import subprocess
-from pathlib import Path
 
 import pytest
 
+import hostprog
 import raftsim
+from hostprog import CSRC, HEADER, ROOT
 from raftsim import _abi
-
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "raftsim.h"
 
 
 def header_functions():
@@ -24,11 +22,7 @@ def test_header_declares_exactly_the_bound_symbols():
 
 
 def test_library_exports_every_header_symbol():
-    assert raftsim.LIB_PATH.exists(), "run __graft_entry__.build() first"
-    out = subprocess.run(["nm", "-D", "--defined-only", str(raftsim.LIB_PATH)],
-                         capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (raft_sim_\w+)", out))
-    missing = set(header_functions()) - exported
+    missing = set(header_functions()) - hostprog.exported(r"raft_sim_\w+")
     assert not missing, missing
     lib = ctypes.CDLL(str(raftsim.LIB_PATH))        # loads without a GPU
     for sym in header_functions():
@@ -63,7 +57,6 @@ def test_source_hash_covers_every_included_project_file():
     assert includes >= 6, "every .hip file includes a project header: the pattern misses them"
 
 
-CSRC =ROOT / "raft-simulation_amd" / "csrc"
 # the compile-time switches csrc/device.hpp declares (diagnostic builds only)
 SWITCHES = ["RS_BURST", "RS_BURST_MIN", "RS_BURST_SKIP", "RS_BURST_DIAG", "RS_WAVELOG"]
 
@@ -72,9 +65,10 @@ SWITCHES = ["RS_BURST", "RS_BURST_MIN", "RS_BURST_SKIP", "RS_BURST_DIAG", "RS_WA
 def test_switches_need_a_diagnostic_build(switch):
     """Setting a kernel switch without RS_DIAG_BUILD is a compile error that names the switch
     (preprocessing only); with RS_DIAG_BUILD it is accepted."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-E", "--cuda-host-only", "-std=c++17", f"-D{switch}=0", "-o", os.devnull,
-           str(CSRC / "tick_kernel.hip")]
+    from raftsim import _build
+
+    cmd = [hostprog.HIPCC, "-E", "--cuda-host-only", "-std=c++17", f"-D{switch}=0", "-o", os.devnull,
+           str(ROOT / _build.UNITS[0])]
     plain = subprocess.run(cmd, capture_output=True, text=True)
     assert plain.returncode != 0
     assert re.search(rf"\b{switch}\b", plain.stderr), plain.stderr
@@ -135,25 +129,7 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     structs = {"raft_sim_config_t": _abi.Config, "raft_node_t": _abi.Node,
                "raft_msg_t": _abi.Msg, "raft_entry_t": _abi.Entry, "raft_cluster_t": _abi.Cluster,
                "raft_counters_t": _abi.Counters}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"',
-             "int main(void) {"]
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(src)], check=True)
-    got = {}
-    for line in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines():
-        c, f, v = line.split()
-        got[(c, f)] = int(v)
-    for cname, cls in structs.items():
-        assert got[(cname, "size")] == ctypes.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert got[(cname, f)] == getattr(cls, f).offset, (cname, f)
+    assert hostprog.c_layout(tmp_path, structs) == []
 
 
 def test_product_fails_loudly_without_gpu():

@@ -3,46 +3,25 @@ argument checks, the Clojure facade's view) and the reference tests/test_gpu_cen
 tests/census_oracle.py, checked on hand-written node records and on the oracle's populations."""
 import ctypes
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
 import census_oracle as co
 import helpers
+import hostprog
 import raftsim
+from hostprog import HEADER, ROOT
 from raftsim import _abi
 from test_gpu_parity import CASES
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "raftsim.h"
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 
 
 def test_layouts_match_the_c_compiler(tmp_path):
     structs = {"raft_census_t": _abi.Census, "raft_cluster_state_t": _abi.ClusterState}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"',
-             "int main(void) {"]
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f, _ in cls._fields_:
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
     names = [f"RAFT_CLS_{k.upper()}" for k in _abi.CLUSTER_CLASSES]
-    lines.append('printf("classes' + " %d" * (len(names) + 1) + '\\n", '
-                 + ", ".join(names) + ", RAFT_CLS_ALL);")
-    lines.append("return 0; }")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(src)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    got = {}
-    for line in out[:-1]:
-        c, f, v = line.split()
-        got[(c, f)] = int(v)
-    for cname, cls in structs.items():
-        assert got[(cname, "size")] == ctypes.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert got[(cname, f)] == getattr(cls, f).offset, (cname, f)
+    out = hostprog.c_layout(tmp_path, structs, ['printf("classes' + " %d" * (len(names) + 1) + '\\n", '
+                                                + ", ".join(names) + ", RAFT_CLS_ALL);"])
     assert ctypes.sizeof(_abi.ClusterState) == 32
     # all of raft_census_t is u64: its fields tile it in 8-byte words, in order
     off = 0
@@ -58,14 +37,11 @@ def test_layouts_match_the_c_compiler(tmp_path):
 
 
 def test_library_exports_exactly_the_census_entry_points():
-    assert raftsim.LIB_PATH.exists(), "run __graft_entry__.build() first"
-    out = subprocess.run(["nm", "-D", "--defined-only", str(raftsim.LIB_PATH)],
-                         capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r"\bT (raft_census_\w+)", out)) == set(_abi.CENSUS_SYMBOLS) == \
+    assert hostprog.exported(r"raft_census_\w+") == set(_abi.CENSUS_SYMBOLS) == \
         {"raft_census_read", "raft_census_select"}
-    assert set(re.findall(r"\bT (raft_viol_\w+)", out)) == {"raft_viol_read", "raft_viol_clear"}
-    assert set(re.findall(r"\bT (raft_sim_\w+)", out)) == set(_abi.PRODUCT_SYMBOLS)
-    assert "T raftsim_diag_census_ms" in out
+    assert hostprog.exported(r"raft_viol_\w+") == {"raft_viol_read", "raft_viol_clear"}
+    assert hostprog.exported(r"raft_sim_\w+") == set(_abi.PRODUCT_SYMBOLS)
+    assert hostprog.exported("raftsim_diag_census_ms")
 
 
 def test_header_declares_the_three_symbol_sets():

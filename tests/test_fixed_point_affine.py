@@ -9,12 +9,7 @@ it checks, for random hashes h, terms T and first heartbeats th:
   * the set of K + 1 rounds made from K's by one step equals the set built directly.
 Ticks: every event tick of a simulation is below 2^32 (the kernels' horizon check), so th is drawn
 such that the last round's last event is; half of the draws end within 10^5 ticks of 2^32 - 1."""
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
+import hostprog
 
 PROGRAM = r"""
 #include <stdint.h>
@@ -108,21 +103,5 @@ int main() {
 """
 
 
-def _runtime(name):
-    out = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True)
-    p = out.stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
 def test_affine_step_equals_events(tmp_path):
-    src, exe = tmp_path / "fpa_check.cpp", tmp_path / "fpa_check"
-    src.write_text(PROGRAM)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o",
-           str(exe)]
-    if _runtime("libubsan.so"):
-        cmd[3:3] = ["-fsanitize=undefined", "-fno-sanitize-recover"]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 20000 and last[3] == "0", r.stdout[-3000:]
+    assert hostprog.checks(hostprog.run_cpp(tmp_path, "fpa_check", PROGRAM)) > 20000

@@ -5,20 +5,18 @@ that raftsim.fork is made of, and the witnesses: the cases the GPU tests run do 
 gather kernel can get wrong."""
 import ctypes
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import gather_mirror as gm
 import helpers
+import hostprog
 import raftsim
+from hostprog import HEADER, ROOT
 from raftsim import ClusterPack, _abi
 from test_gpu_parity import CASES, FAULTS
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "raftsim.h"
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 NONE64 = 2 ** 64 - 1
 
@@ -42,26 +40,15 @@ def run_oracle(cfg, ticks):
 
 
 def test_layouts_match_the_c_compiler(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"',
-             "int main(void) {",
-             'printf("sizeof %zu\\n", sizeof(raft_gather_layout_t));']
-    for f, _ in _abi.GatherLayout._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(raft_gather_layout_t, {f}));')
     names = [f"RAFT_GATHER_{k.upper()}" for k in _abi.GATHER_PARTS]
-    lines.append('printf("parts' + " %d" * (len(names) + 1) + '\\n", '
-                 + ", ".join(names) + ", RAFT_GATHER_ALL);")
-    lines.append('printf("records %zu %zu %zu %zu\\n", sizeof(raft_cluster_t), '
-                 'sizeof(raft_node_t), sizeof(raft_msg_t), sizeof(raft_entry_t));')
-    lines.append("return 0; }")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(src)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    got = dict((line.split()[0], int(line.split()[1])) for line in out[:-2])
-    assert got["sizeof"] == ctypes.sizeof(_abi.GatherLayout) == 104
+    out = hostprog.c_layout(tmp_path, {"raft_gather_layout_t": _abi.GatherLayout}, [
+        'printf("parts' + " %d" * (len(names) + 1) + '\\n", ' + ", ".join(names) + ", RAFT_GATHER_ALL);",
+        'printf("records %zu %zu %zu %zu\\n", sizeof(raft_cluster_t), '
+        'sizeof(raft_node_t), sizeof(raft_msg_t), sizeof(raft_entry_t));'])
+    assert ctypes.sizeof(_abi.GatherLayout) == 104
     off = 0
     for f, t in _abi.GatherLayout._fields_:              # all u64, tiling the structure in order
-        assert got[f] == getattr(_abi.GatherLayout, f).offset == off, f
+        assert getattr(_abi.GatherLayout, f).offset == off, f
         assert (t._type_ if hasattr(t, "_length_") else t) is ctypes.c_uint64, f
         off += ctypes.sizeof(t)
     assert off == 104
@@ -104,17 +91,14 @@ def test_layout_arithmetic(shape, parts, want):
 
 
 def test_library_exports_exactly_the_gather_entry_points():
-    assert raftsim.LIB_PATH.exists(), "run __graft_entry__.build() first"
-    out = subprocess.run(["nm", "-D", "--defined-only", str(raftsim.LIB_PATH)],
-                         capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r"\bT (raft_gather_\w+)", out)) == set(_abi.GATHER_SYMBOLS) == \
+    assert hostprog.exported(r"raft_gather_\w+") == set(_abi.GATHER_SYMBOLS) == \
         {"raft_gather_layout", "raft_gather_read"}
-    assert "T raftsim_diag_gather_ms" in out
+    assert hostprog.exported("raftsim_diag_gather_ms")
     # the older sets are what they were
-    assert set(re.findall(r"\bT (raft_audit_\w+)", out)) == set(_abi.AUDIT_SYMBOLS)
-    assert set(re.findall(r"\bT (raft_census_\w+)", out)) == set(_abi.CENSUS_SYMBOLS)
-    assert set(re.findall(r"\bT (raft_viol_\w+)", out)) == set(_abi.VIOL_SYMBOLS)
-    assert set(re.findall(r"\bT (raft_sim_\w+)", out)) == set(_abi.PRODUCT_SYMBOLS)
+    assert hostprog.exported(r"raft_audit_\w+") == set(_abi.AUDIT_SYMBOLS)
+    assert hostprog.exported(r"raft_census_\w+") == set(_abi.CENSUS_SYMBOLS)
+    assert hostprog.exported(r"raft_viol_\w+") == set(_abi.VIOL_SYMBOLS)
+    assert hostprog.exported(r"raft_sim_\w+") == set(_abi.PRODUCT_SYMBOLS)
 
 
 def test_header_declares_the_gather():
@@ -134,9 +118,6 @@ def test_header_declares_the_gather():
     # the kernel is part of the build and of its hash
     from raftsim import _build
     assert "raft-simulation_amd/csrc/gather_kernel.hip" in _build.KERNEL_SOURCES
-    entry = (ROOT / "__graft_entry__.py").read_text()
-    sources = re.search(r"HIP_SOURCES = \[(.*?)\]", entry, re.S).group(1)
-    assert '"gather_kernel.hip"' in sources
 
 
 def test_bad_arguments_are_refused_without_a_device():

@@ -37,12 +37,7 @@ RESORT_EVERY_LITE -- from the keys launch 7 wrote, which is what the code before
 scatter, which is the next expectation: after set_tick the next rebuild computes its keys); a
 steady launch between the launch that wrote keys and the rebuild makes the rebuild compute them;
 path_exists is N <= 5 without Spec-Raft for the steady kernel, no Spec-Raft for LITE, N = 2..9."""
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
+import hostprog
 
 PROGRAM = r"""
 #include <stdint.h>
@@ -677,23 +672,7 @@ int main() {
 """
 
 
-def _runtime(name):
-    out = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True)
-    p = out.stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
 def test_the_planner_is_the_old_policy_and_the_policy_is_what_the_words_say(tmp_path):
-    src, exe = tmp_path / "launch_plan_check.cpp", tmp_path / "launch_plan_check"
-    src.write_text(PROGRAM)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o",
-           str(exe)]
-    if _runtime("libubsan.so") and _runtime("libasan.so"):
-        cmd[3:3] = ["-fsanitize=undefined,address", "-fno-sanitize-recover"]
-    elif _runtime("libubsan.so"):
-        cmd[3:3] = ["-fsanitize=undefined", "-fno-sanitize-recover"]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 10000000 and last[3] == "0", r.stdout[-3000:]
+    out = hostprog.run_cpp(tmp_path, "launch_plan_check", PROGRAM,
+                           sanitizers=("undefined", "address"), timeout=300)
+    assert hostprog.checks(out) > 10000000

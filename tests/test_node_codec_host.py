@@ -20,14 +20,7 @@ extreme values of every packed field (device.hpp's packed_check):
 5. queue words: counts 0, 1 and Q on each side give pack_qmeta(0, rq, 0, rs), arrival INF / the
    first message's, tail 0 / the last one's; putting one ring into HF_QMETA keeps the other's head
    and count."""
-import glob
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import hostprog
 
 PROGRAM = r"""
 #include <stdint.h>
@@ -331,21 +324,7 @@ int main() {
 """
 
 
-def _sanitizers():
-    """The sanitizer flags, where hipcc's clang has both runtimes for the host."""
-    rt = str(Path(os.path.realpath(HIPCC)).parent.parent / "lib/llvm/lib/clang/*/lib/linux")
-    if not all(glob.glob(f"{rt}/libclang_rt.{n}-x86_64.a") for n in ("asan", "ubsan_standalone")):
-        return []
-    return ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
-
-
 def test_the_codec_is_the_by_member_mapping_in_both_directions(tmp_path):
-    src, exe = tmp_path / "codec_check.cpp", tmp_path / "codec_check"
-    src.write_text(PROGRAM)
-    subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-Wall",
-                    "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o", str(exe), *_sanitizers()],
-                   check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 50000 and last[3] == "0", r.stdout[-3000:]
+    out = hostprog.run_cpp(tmp_path, "codec_check", PROGRAM, compiler="hipcc",
+                           sanitizers=("address", "undefined"))
+    assert hostprog.checks(out) > 50000

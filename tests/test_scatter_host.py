@@ -19,12 +19,7 @@ predicate a record that breaks only that clause is refused with that clause's co
 message; a queue's count is its node record's; a client cursor or a queued client-set marks the
 record as needing the general kernel; first_duplicate finds the second occurrence with the
 smallest position."""
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
+import hostprog
 
 PROGRAM = r"""
 #include <stdint.h>
@@ -325,23 +320,7 @@ int main() {
 """
 
 
-def _runtime(name):
-    out = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True)
-    p = out.stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
 def test_the_planner_places_every_pair_once_and_the_predicates_refuse_by_clause(tmp_path):
-    src, exe = tmp_path / "scatter_check.cpp", tmp_path / "scatter_check"
-    src.write_text(PROGRAM)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o",
-           str(exe)]
-    if _runtime("libubsan.so") and _runtime("libasan.so"):
-        cmd[3:3] = ["-fsanitize=undefined,address", "-fno-sanitize-recover"]
-    elif _runtime("libubsan.so"):
-        cmd[3:3] = ["-fsanitize=undefined", "-fno-sanitize-recover"]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 1000000 and last[3] == "0", r.stdout[-3000:]
+    out = hostprog.run_cpp(tmp_path, "scatter_check", PROGRAM, sanitizers=("undefined", "address"),
+                           timeout=300)
+    assert hostprog.checks(out) > 1000000

@@ -10,12 +10,7 @@ rho ? P : 0). A stand-alone C++ program (its own main, the header alone) is comp
 under UBSan where the machine has its runtime -- and compares the two for F = 1..4, d = 1..3,
 hb from 2d + F to 2d + F + 40 and 3000, every nt in 0 .. 4P + last + 2 plus 10,000 and 65,536, and
 every delta in [0, P)."""
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
+import hostprog
 
 PROGRAM = r"""
 #include <stdint.h>
@@ -64,21 +59,6 @@ int main() {
 """
 
 
-def _runtime(name):
-    out = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True)
-    p = out.stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
 def test_band_equals_division(tmp_path):
-    src, exe = tmp_path / "band_check.cpp", tmp_path / "band_check"
-    src.write_text(PROGRAM)
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o",
-           str(exe)]
-    if _runtime("libubsan.so"):
-        cmd[3:3] = ["-fsanitize=undefined", "-fno-sanitize-recover"]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 100_000_000 and last[3] == "0", r.stdout[-3000:]
+    out = hostprog.run_cpp(tmp_path, "band_check", PROGRAM, opt="-O2")
+    assert hostprog.checks(out) > 100_000_000

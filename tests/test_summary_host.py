@@ -19,14 +19,9 @@ is the identity of fold; fold is commutative and associative on random triples; 
 k summary_combine's give the field-wise fold computed directly, the structs written and read
 through their member names in raftsim/_abi.py's order."""
 import ctypes
-import os
-import subprocess
-from pathlib import Path
 
+import hostprog
 from raftsim import _abi
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "raft-simulation_amd" / "csrc"
 
 MINIMA = {"census": ("term_min",),
           "audit": ("agree_min", "diverge_index_min", "commit_diverge_index_min")}
@@ -194,22 +189,7 @@ def tables(who, struct):
                       f"static void get_{who}(const raft_{who}_t& s, uint64_t* v) {{", *get, "}"])
 
 
-def _runtime(name):
-    out = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True)
-    p = out.stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
 def test_layout_regions_are_disjoint_and_the_algebra_folds_by_name(tmp_path):
-    src, exe = tmp_path / "summary_check.cpp", tmp_path / "summary_check"
-    src.write_text(PROGRAM.replace("@TABLES@", tables("census", _abi.Census) + "\n" +
-                                   tables("audit", _abi.Audit)))
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"-I{CSRC}", str(src), "-o",
-           str(exe)]
-    if _runtime("libubsan.so"):
-        cmd[3:3] = ["-fsanitize=undefined", "-fno-sanitize-recover"]
-    subprocess.run(cmd, check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr, r.stdout[-3000:] + r.stderr[-3000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "checks" and int(last[1]) > 100000 and last[3] == "0", r.stdout[-3000:]
+    program = PROGRAM.replace("@TABLES@", tables("census", _abi.Census) + "\n" +
+                              tables("audit", _abi.Audit))
+    assert hostprog.checks(hostprog.run_cpp(tmp_path, "summary_check", program)) > 100000

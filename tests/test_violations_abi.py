@@ -4,38 +4,24 @@ rests on, checked on the oracle alone: one-cluster oracle handles give per-clust
 sums are the whole handle's counters."""
 import ctypes
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
 import helpers
+import hostprog
 import raftsim
 import viol_oracle
+from hostprog import HEADER, ROOT
 from raftsim import _abi, _backend
 from test_gpu_parity import CASES
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "raftsim.h"
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 
 
 def test_violation_layout_matches_the_c_compiler(tmp_path):
-    cname, cls = "raft_violation_t", _abi.Violation
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"',
-             "int main(void) {", f'printf("size %zu\\n", sizeof({cname}));']
-    for f, _ in cls._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof({cname}, {f}));')
-    lines += ['printf("kinds %d %d %d\\n", RAFT_VIOL_ELECTION, RAFT_VIOL_LOG, RAFT_VIOL_COMPLETE);',
-              "return 0; }"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(src)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    got = dict(line.split(maxsplit=1) for line in out[:-1])
-    assert int(got["size"]) == ctypes.sizeof(cls) == 24
-    for f, _ in cls._fields_:
-        assert int(got[f]) == getattr(cls, f).offset, f
+    out = hostprog.c_layout(tmp_path, {"raft_violation_t": _abi.Violation}, [
+        'printf("kinds %d %d %d\\n", RAFT_VIOL_ELECTION, RAFT_VIOL_LOG, RAFT_VIOL_COMPLETE);'])
+    assert ctypes.sizeof(_abi.Violation) == 24
     assert out[-1].split()[1:] == [str(_abi.VIOL_KINDS[k]) for k in viol_oracle.KINDS]
     # the per-kind counts follow the counter enum's order (the kernel indexes them by it)
     i = _abi.COUNTER_NAMES.index("viol_election")
@@ -43,11 +29,8 @@ def test_violation_layout_matches_the_c_compiler(tmp_path):
 
 
 def test_library_exports_the_violation_entry_points():
-    assert raftsim.LIB_PATH.exists(), "run __graft_entry__.build() first"
-    out = subprocess.run(["nm", "-D", "--defined-only", str(raftsim.LIB_PATH)],
-                         capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (raft_viol_\w+)", out))
-    assert exported == set(_abi.VIOL_SYMBOLS) == {"raft_viol_read", "raft_viol_clear"}
+    assert hostprog.exported(r"raft_viol_\w+") == set(_abi.VIOL_SYMBOLS) == \
+        {"raft_viol_read", "raft_viol_clear"}
     lib = ctypes.CDLL(str(raftsim.LIB_PATH))        # loads without a GPU
     fns = _abi.bind(lib, "raft_viol_", sigs=_abi._VIOL_SIGS)
     assert set(fns) == {"read", "clear"}
