@@ -339,6 +339,25 @@
     (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
     rc))
 
+(defn clone
+  "Cluster state copied on the device (raft_clone_write): cluster (nth ts i) of `dst` becomes the
+  state of cluster (nth ss i) of `src`, which may be dst, as a scatter of a gather would leave it,
+  with no pack in host memory. A source may be named any number of times (one state, many futures),
+  a target once, and within one handle no cluster may be both. The handles must agree in nodes,
+  inbox-cap, log-cap, arena-cap and commit-stream-cap and live on one GPU. Does not set a clock
+  (set-tick!). Returns the number of clusters written."
+  [dst ts src ss]
+  (let [n (count ts)
+        _ (when (not= n (count ss))
+            (throw (ex-info "clone: as many sources as targets" {:targets n :sources (count ss)})))
+        ints (fn [xs] (let [m (Memory. (* 4 (max 1 n)))]
+                        (doseq [[i x] (map-indexed vector xs)] (.setInt m (* 4 i) (unchecked-int x)))
+                        m))
+        rc (.invokeLong (f "raft_clone_write")
+                        (object-array [(:ptr dst) (ints ts) (:ptr src) (ints ss) (int n)]))]
+    (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
+    rc))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

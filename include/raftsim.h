@@ -469,6 +469,44 @@ int64_t raft_gather_read(raft_sim_t* sim, const uint32_t* clusters, uint32_t n, 
 int64_t raft_scatter_write(raft_sim_t* sim, const uint32_t* clusters, const uint32_t* records,
                            uint32_t n, uint32_t parts, const void* in, uint32_t n_records);
 
+/* ---- Cluster clones (no reference counterpart, none in the oracle) --------------------------
+ * Cluster state copied from cluster to cluster on the device, within one handle or between two on
+ * the same GPU, without a pack in host memory between them: cluster targets[i] of `dst` becomes the
+ * state of cluster sources[i] of `src` as it stands. `src` may be `dst`; a source may be named any
+ * number of times (one state placed at K cluster ids is K independent futures of it: Philox is
+ * keyed by the global cluster id), a target once. All indices are local to their handle, in any
+ * order, across shards. Returns the number of clusters written.
+ *
+ * The target is bit for bit what raft_scatter_write of the one-record pack raft_gather_read gives
+ * for the source (parts CLUSTER | NODES | QUEUES | ARENAS, and STREAMS when commit_stream_cap > 0)
+ * leaves: an owed timer draw of the source is resolved with the source's global id and seed and
+ * stored as the exact deadline; the reserved cluster words (the steady certificate) and the block's
+ * padding are zero; each queue ring is rewritten head first from slot 0 with the slots at and past
+ * its count zero; the raw arenas and commit_count are copied; commit-stream slots outside the
+ * newest min(commit_count, commit_stream_cap) values are zero. Every source is read as it was
+ * before the call. Like the scatter, the call touches neither handle's clock, violation records,
+ * counters or trace rings; it only reads the source, whose digest, audit records and steady
+ * certificate stay and whose next step runs as it would have.
+ *
+ * The handles must agree in nodes, inbox_cap, log_cap, the effective arena_cap (0 means 4 *
+ * log_cap) and commit_stream_cap. Timers, rates, seed, variant, trace caps and n_devices may
+ * differ: the target then continues the state under its own handle's config and global id, which
+ * is the source's own future only when timers, rates, seed, variant and the cluster's global id
+ * agree as well (a handle created from the source's config at the same cluster_offset).
+ *
+ * -EINVAL: a null handle, a null list with n > 0, an index >= n_clusters of its handle, a target
+ * named twice, with src == dst a cluster that is both a source and a target, handles that differ
+ * in one of the five fields above (the message names it); the message names the first offending
+ * position. -EXDEV: a pair whose source shard and target shard live on different HIP devices: that
+ * path needs peer copies and stays with raft_gather_read + raft_scatter_write; shards that share a
+ * device clone across their boundaries. -EIO: a HIP error, or a poisoned handle. All refusals come
+ * before any device is touched: the call writes every target or none. n == 0 returns 0 and
+ * launches nothing. Synchronous like the other writes: stream-ordered after everything enqueued on
+ * both handles (valid after raft_sim_step_async), then waited for. Only the list of pairs is
+ * uploaded, through the target's gather scratch (8 bytes a pair, 64 MiB per device at a time). */
+int64_t raft_clone_write(raft_sim_t* dst, const uint32_t* targets, raft_sim_t* src,
+                         const uint32_t* sources, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

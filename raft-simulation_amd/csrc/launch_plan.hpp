@@ -286,6 +286,13 @@ constexpr uint32_t ON_SET_TICK = INV_STORM | INV_KEYS;
 constexpr uint32_t ON_SCATTER = INV_STORM | INV_AUDIT | INV_KEYS;
 // ... and when one of the shard's records needs the general kernel (scatter_host.hpp)
 constexpr uint32_t ON_SCATTER_GENERAL = INV_LITE;
+// raft_clone_write, per touched target shard: what a scatter of the same clusters marks, and like
+// it after every check (a refused clone has touched nothing; the source shards are only read and
+// keep their state) ...
+constexpr uint32_t ON_CLONE = ON_SCATTER;
+// ... and when a shard it reads from is no longer LITE: a cloned cluster may then carry a finite
+// client cursor or a queued client-set (no record is looked at on the host)
+constexpr uint32_t ON_CLONE_GENERAL = ON_SCATTER_GENERAL;
 
 inline void invalidate(LaunchState& s, uint32_t what) {
   if (what & INV_STORM) s.storm_until = 0;

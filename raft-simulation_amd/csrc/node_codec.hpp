@@ -4,8 +4,10 @@
 //   node_word   hot block -> record (raft_sim_read_nodes, gather_kernel), resolving an owed timer draw
 //   hot_field   record -> hot block (raft_sim_write_nodes, scatter_kernel), FL_DRAW clear
 //   ring_words  what a queue ring contributes to the hot block (raft_sim_write_queue, scatter_kernel)
-// Host and device: compiles for the CPU alone too (tests/test_node_codec_host.py checks all three
-// against a by-member-name statement of the same mapping).
+//   hot_clone   hot block -> hot block (clone_kernel): hot_field of node_word without the record
+// Host and device: compiles for the CPU alone too (tests/test_node_codec_host.py checks the first
+// three against a by-member-name statement of the same mapping, tests/test_clone_host.py the fourth
+// against the first two).
 #pragma once
 #include <stddef.h>
 
@@ -122,6 +124,22 @@ __host__ __device__ __forceinline__ uint32_t hot_field(const uint32_t* nw, uint3
   }
 }
 
+// Field f (< hot_fields(N), not hf_is_queue) of a node as hot_field(nw, N, f) gives it for the record
+// nw[w] = node_word(h, N, w, cc, g, k, dk), without the record: the deadline is the exact draw, the
+// flags keep their six fields (FL_DRAW and the unused bits above it are no field of a record), and
+// every other field is the source's word (votes and ls_keys are the two halves of HF_MASKS; the peer
+// rows are N fields each on both sides).
+__host__ __device__ __forceinline__ uint32_t hot_clone(const uint32_t* h, uint32_t N, uint32_t f,
+                                                       uint32_t g, uint32_t k, const DrawKeys& dk) {
+  const uint32_t v = h[f * N];
+  if (f == HF_DEADLINE)
+    return h[HF_FLAGS * N] & FL_DRAW
+               ? exact_deadline(g, k + 1, v, dk.el_base, dk.el_span, dk.key0, dk.key1)
+               : v;
+  if (f == HF_FLAGS) return v & (FL_ROLE | FL_VF | FL_LID | FL_FAULT | FL_SEQ | FL_LSP);
+  return v;
+}
+
 // What a ring of `count` messages contributes to its node's hot words, as raft_sim_write_queue
 // leaves them: its half (mask) of HF_QMETA with head 0, the first message's arrival (INF when
 // empty) and the last one's (0 when empty). msgs: the messages in order from the head, MSG_WORDS
@@ -129,27 +147,44 @@ __host__ __device__ __forceinline__ uint32_t hot_field(const uint32_t* nw, uint3
 struct RingWords {
   uint32_t mask, qmeta, arr, tail;
 };
+// (first, last: the arrivals of the first and the last message, looked at only when count > 0)
+__host__ __device__ __forceinline__ RingWords ring_words(uint32_t which, uint32_t count,
+                                                         uint32_t first, uint32_t last) {
+  return {which ? QM_RES : QM_REQ, which ? pack_qmeta(0, 0, 0, count) : pack_qmeta(0, count, 0, 0),
+          count ? first : INF, count ? last : 0u};
+}
 __host__ __device__ __forceinline__ RingWords ring_words(uint32_t which, uint32_t count,
                                                          const uint32_t* msgs) {
-  return {which ? QM_RES : QM_REQ, which ? pack_qmeta(0, 0, 0, count) : pack_qmeta(0, count, 0, 0),
-          count ? msgs[0] : INF, count ? msgs[(size_t)(count - 1) * MSG_WORDS] : 0u};
+  return ring_words(which, count, count ? msgs[0] : INF,
+                    count ? msgs[(size_t)(count - 1) * MSG_WORDS] : 0u);
 }
 // HF_QMETA with that ring put in; the other ring's head and count stay.
 __host__ __device__ __forceinline__ uint32_t with_ring(uint32_t qm, const RingWords& r) {
   return (qm & ~r.mask) | r.qmeta;
 }
-// Field f (hf_is_queue) of a node whose REQ ring holds the rqc messages at rq and whose RES ring the
-// rsc messages at rs.
+// Field f (hf_is_queue) of a node whose REQ ring contributes rq() and whose RES ring rs(): each is
+// asked only for the fields that need it (a ring's words may cost two loads).
+template <typename RQ, typename RS>
+__host__ __device__ __forceinline__ uint32_t queue_field_of(uint32_t f, const RQ& rq, const RS& rs) {
+  switch (f) {
+    case HF_QMETA: return with_ring(rq().qmeta, rs());
+    case HF_REQ_ARR: return rq().arr;
+    case HF_RES_ARR: return rs().arr;
+    case HF_REQ_TAIL: return rq().tail;
+    default: return rs().tail;
+  }
+}
+// ... of a node whose REQ ring holds the rqc messages at rq and whose RES ring the rsc messages at rs
 __host__ __device__ __forceinline__ uint32_t queue_field(uint32_t f, uint32_t rqc,
                                                          const uint32_t* rq, uint32_t rsc,
                                                          const uint32_t* rs) {
-  switch (f) {
-    case HF_QMETA: return with_ring(ring_words(0, rqc, rq).qmeta, ring_words(1, rsc, rs));
-    case HF_REQ_ARR: return ring_words(0, rqc, rq).arr;
-    case HF_RES_ARR: return ring_words(1, rsc, rs).arr;
-    case HF_REQ_TAIL: return ring_words(0, rqc, rq).tail;
-    default: return ring_words(1, rsc, rs).tail;
-  }
+  return queue_field_of(f, [=] { return ring_words(0, rqc, rq); },
+                        [=] { return ring_words(1, rsc, rs); });
+}
+// ... of a node whose rings contribute the words rq and rs
+__host__ __device__ __forceinline__ uint32_t queue_field(uint32_t f, const RingWords& rq,
+                                                         const RingWords& rs) {
+  return queue_field_of(f, [&] { return rq; }, [&] { return rs; });
 }
 
 }  // namespace rs

@@ -1,7 +1,9 @@
 // pack.hpp — what gather_kernel.hip and scatter_kernel.hip share (cluster packs, include/raftsim.h):
 // the launch shape, a workgroup's share of the list and of a record, and how the elements of the
 // queue and arena parts are numbered. A record is a pack record, and for the scatter one (record,
-// target) pair.
+// target) pair. clone_kernel (scatter_kernel.hip), which copies cluster to cluster without a record,
+// takes the same shape over its (target, source) pairs, and from here the two decisions it shares
+// with the host tests: the width of an arena access and which commit-stream slots a pack keeps.
 #pragma once
 #include <algorithm>
 
@@ -49,6 +51,28 @@ __device__ __forceinline__ QueueElem queue_elem(uint32_t i, uint32_t Q) {
 // one), else as 8-byte accesses. s: a slot counted from cluster c's first.
 __device__ __forceinline__ bool arena_even(const DevSim& S, uint32_t c, uint32_t s) {
   return (((size_t)c * S.N * S.A + s) & 1) == 0;
+}
+
+// The same decision for a copy from arena to arena (clone_kernel), where either side may stand on
+// an odd slot, taken for each side alone: the bytes of the access that moves entry e and, where it
+// exists, entry e + 1 (e even) of the `entries` of a cluster whose first arena slot is slot0 of its
+// shard's arenas (c * N * A; the arenas start on 16 bytes). 16 only where that side's entry e lies
+// on an even slot, i.e. on 16 bytes, and entry e + 1 exists.
+__host__ __device__ constexpr uint32_t arena_access_bytes(uint64_t slot0, uint32_t e,
+                                                          uint32_t entries) {
+  return ((slot0 + e) & 1) == 0 && e + 1 < entries ? 16u : 8u;
+}
+
+// Whether slot s of a node's commit-stream ring (SC slots, commit_count cc) holds one of the values
+// a pack keeps, the newest kept = min(cc, SC). gather_kernel writes value p < kept of a record from
+// slot (cc - kept + p) mod SC, and scatter_kernel writes into slot s the record's value
+// p = (s - (cc - kept)) mod SC when p < kept, else 0. For that p the gather's slot is
+// (cc - kept + p) mod SC = s: a scatter of a gather leaves slot s of the target with slot s of the
+// source where p < kept, and with 0 elsewhere -- the ring is not rotated, only cleared outside the
+// kept window.
+__host__ __device__ constexpr bool stream_slot_kept(uint32_t s, uint32_t cc, uint32_t SC) {
+  const uint32_t kept = cc < SC ? cc : SC;
+  return (s + SC - (cc - kept) % SC) % SC < kept;
 }
 
 }  // namespace rs

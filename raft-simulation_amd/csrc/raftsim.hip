@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "clone_host.hpp"
 #include "launch_plan.hpp"
 #include "node_codec.hpp"
 #include "scatter_host.hpp"
@@ -45,6 +46,8 @@ hipError_t launch_gather(const DevSim& S, const void* pairs, uint32_t n,
 // scatter_kernel.hip
 hipError_t launch_scatter(const DevSim& S, const void* pairs, uint32_t n,
                           const raft_gather_layout_t& Y, const void* in, hipStream_t st);
+hipError_t launch_clone(const DevSim& T, const DevSim& Src, const void* pairs, uint32_t n,
+                        uint64_t stride, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -117,6 +120,11 @@ struct Shard {
   // times its chunks' kernels with the same events (raftsim_diag_scatter_ms); pack_scratch,
   // pack_events and pack_wait below serve both calls.
   double scatter_ms;
+  // raft_clone_write (clone_kernel, scatter_kernel.hip) uploads its lists of pairs into the same
+  // scratch and times its chunks' kernels with the same events (raftsim_diag_clone_ms). cev: as a
+  // source shard, the event the target shard's stream waits for before it reads this shard.
+  hipEvent_t cev;
+  double clone_ms;
 };
 
 // Exported functions take their C linkage from the declarations in include/raftsim.h.
@@ -190,6 +198,7 @@ static void sh_destroy(Shard* s) {
   if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
   if (s->qev0) (void)hipEventDestroy(s->qev0);
   if (s->qev1) (void)hipEventDestroy(s->qev1);
+  if (s->cev) (void)hipEventDestroy(s->cev);
   for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->gev) (void)hipEventDestroy(e);
   if (s->gscratch) (void)hipFree(s->gscratch);
@@ -292,6 +301,7 @@ static int sh_init(Shard* s, const raft_sim_config_t* cfg) {
       (e = hipEventCreate(&s->ev_stop)) != hipSuccess ||
       (e = hipEventCreate(&s->qev0)) != hipSuccess ||
       (e = hipEventCreate(&s->qev1)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&s->cev, hipEventDisableTiming)) != hipSuccess ||
       (e = hipMemsetAsync(d.hot, 0, (size_t)s->C * d.HB * 4, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.qbuf, 0, NN * 2 * s->Q * 32, s->stream)) != hipSuccess ||
       (e = hipMemsetAsync(d.arena, 0, (NN * (size_t)s->A + rs::ARENA_PAD_SLOTS) * 8, s->stream)) != hipSuccess ||
@@ -1617,6 +1627,145 @@ int64_t raft_scatter_write(raft_sim_t* r, const uint32_t* clusters, const uint32
 // in ms.
 extern "C" int raftsim_diag_scatter_ms(raft_sim_t* r, double* ms) {
   return diag_ms(r, ms, &Shard::scatter_ms);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cluster clones: the scatter of a gather without the pack (include/raftsim.h, "Cluster clones").
+// Everything that can refuse the call is checked on the host first (clone_host.hpp: the ranges, a
+// target named twice, a cluster both read and written; here the handles' shapes and devices), so a
+// refused call has touched no device. The (target, source) pairs are grouped by the shards they
+// join and cut into chunks of the target shard's scratch (the gather's, GATHER_SCRATCH_BYTES at 8
+// bytes a pair): a chunk's list is uploaded and one kernel writes its targets from the source
+// shard's state. A target shard's stream first waits for an event on the stream of every other
+// shard it reads, so the call is ordered after everything enqueued on both handles; the chunks of a
+// shard follow each other on its stream, all target shards run at once, and every started shard is
+// waited for (pack_wait). The host's bookkeeping of a touched target shard is a scatter's; a
+// source shard is only read.
+int64_t raft_clone_write(raft_sim_t* dst, const uint32_t* targets, raft_sim_t* src,
+                         const uint32_t* sources, uint32_t n) {
+  if (!dst || !src) return fail(-EINVAL, "null sim");
+  if (n && !targets) return fail(-EINVAL, "null target list");
+  if (n && !sources) return fail(-EINVAL, "null source list");
+  char what[200];
+  {
+    const Shard *t = dst->sh[0], *s = src->sh[0];
+    const struct {
+      const char* name;
+      uint32_t dst, src;
+    } shape[] = {{"nodes", t->N, s->N},
+                 {"inbox_cap", t->Q, s->Q},
+                 {"log_cap", t->L, s->L},
+                 {"arena_cap", t->A, s->A},
+                 {"commit_stream_cap", t->cfg.commit_stream_cap, s->cfg.commit_stream_cap}};
+    for (const auto& f : shape)
+      if (f.dst != f.src) {
+        snprintf(what, sizeof what, "the handles differ in %s: the target's is %u, the source's %u",
+                 f.name, f.dst, f.src);
+        return fail(-EINVAL, "%s", what);
+      }
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const bool t_out = targets[i] >= dst->cfg.n_clusters;
+    if (!t_out && sources[i] < src->cfg.n_clusters) continue;
+    snprintf(what, sizeof what, "%s[%u] = %u is outside the handle's %u clusters",
+             t_out ? "targets" : "sources", i, t_out ? targets[i] : sources[i],
+             t_out ? dst->cfg.n_clusters : src->cfg.n_clusters);
+    return fail(-EINVAL, "%s", what);
+  }
+  const uint32_t dup = rs::first_duplicate(targets, n);
+  if (dup < n) {
+    snprintf(what, sizeof what, "targets[%u] = %u is a target twice", dup, targets[dup]);
+    return fail(-EINVAL, "%s", what);
+  }
+  if (src == dst) {
+    bool target_is_source = false;
+    const uint32_t at = rs::first_source_target(targets, sources, n, &target_is_source);
+    if (at < n) {
+      snprintf(what, sizeof what, "%s[%u] = %u is both a source and a target of the handle",
+               target_is_source ? "targets" : "sources", at,
+               target_is_source ? targets[at] : sources[at]);
+      return fail(-EINVAL, "%s", what);
+    }
+  }
+  const size_t TG = dst->sh.size(), SG = src->sh.size();
+  const rs::ClonePlan plan =
+      rs::clone_plan(targets, dst->lo.data(), (uint32_t)TG, sources, src->lo.data(), (uint32_t)SG, n,
+                     GATHER_SCRATCH_BYTES / sizeof(rs::ClonePair));
+  uint32_t far = UINT32_MAX;                     // the first position that joins two devices
+  for (const rs::CloneChunk& ch : plan.chunks)
+    if (dst->sh[ch.dst_shard]->cfg.device != src->sh[ch.src_shard]->cfg.device)
+      far = std::min(far, *std::min_element(plan.pos.begin() + ch.pair0,
+                                            plan.pos.begin() + ch.pair0 + ch.pairs));
+  if (far != UINT32_MAX) {
+    snprintf(what, sizeof what, "sources[%u] = %u and targets[%u] = %u live on different devices: "
+             "clone across devices through raft_gather_read and raft_scatter_write", far,
+             sources[far], far, targets[far]);
+    return fail(-EXDEV, "%s", what);
+  }
+  if (dst->poisoned || src->poisoned) return unusable();
+  if (!n) return 0;
+
+  raft_gather_layout_t Y;
+  gather_layout_of(dst->sh[0],
+                   RAFT_GATHER_CLUSTER | RAFT_GATHER_NODES | RAFT_GATHER_QUEUES | RAFT_GATHER_ARENAS |
+                       (dst->cfg.commit_stream_cap ? RAFT_GATHER_STREAMS : 0),
+                   &Y);
+  // Per target shard: its chunks [first, first + count) of the plan, and whether it reads a shard
+  // that is no longer LITE (asked before any shard is marked: src may be dst).
+  std::vector<size_t> first(TG, 0), count(TG, 0);
+  std::vector<uint8_t> general(TG, 0), read(SG, 0);
+  for (size_t i = 0; i < plan.chunks.size(); ++i) {
+    const rs::CloneChunk& ch = plan.chunks[i];
+    if (!count[ch.dst_shard]) first[ch.dst_shard] = i;
+    ++count[ch.dst_shard];
+    general[ch.dst_shard] |= !src->sh[ch.src_shard]->ls.lite;
+    read[ch.src_shard] = 1;
+  }
+  PackCall hip = {"raft_clone_write"};
+  for (size_t e = 0; e < SG && !hip.rc; ++e)
+    if (read[e])
+      hip.step(hipSetDevice(src->sh[e]->cfg.device)) &&
+          hip.step(hipEventRecord(src->sh[e]->cev, src->sh[e]->stream));
+  std::vector<size_t> started;
+  for (size_t d = 0; d < TG && !hip.rc; ++d) {
+    if (!count[d]) continue;
+    Shard* s = dst->sh[d];
+    started.push_back(d);
+    if (!hip.step(hipSetDevice(s->cfg.device))) break;
+    rs::invalidate(s->ls, rs::ON_CLONE);
+    if (general[d]) rs::invalidate(s->ls, rs::ON_CLONE_GENERAL);
+    size_t need = 0;
+    for (size_t i = first[d]; i < first[d] + count[d]; ++i)
+      need = std::max(need, plan.chunks[i].pairs * sizeof(rs::ClonePair));
+    if (!pack_scratch(hip, s, need) || !pack_events(hip, s, count[d])) break;
+    const Shard* waited = nullptr;               // a shard's chunks stand source shard by source shard
+    for (size_t i = 0; i < count[d] && !hip.rc; ++i) {
+      const rs::CloneChunk& ch = plan.chunks[first[d] + i];
+      const Shard* q = src->sh[ch.src_shard];
+      if (q != s && q != waited && !hip.step(hipStreamWaitEvent(s->stream, q->cev, 0))) break;
+      waited = q;
+      hip.step(hipMemcpyAsync(s->gscratch, plan.pairs.data() + ch.pair0,
+                              ch.pairs * sizeof(rs::ClonePair), hipMemcpyHostToDevice,
+                              s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i], s->stream)) &&
+          hip.step(rs::launch_clone(s->d, q->d, s->gscratch, (uint32_t)ch.pairs, Y.stride,
+                                    s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i + 1], s->stream));
+    }
+  }
+  // every started shard is waited for, also after an error: its uploads read the plan
+  for (size_t d : started) pack_wait(hip, dst->sh[d], count[d], &Shard::clone_ms);
+  if (!hip.rc)
+    for (size_t d = 0; d < TG; ++d)
+      if (!count[d]) dst->sh[d]->clone_ms = 0;
+  return hip.rc ? hip.rc : (int64_t)n;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_clone_write's kernels
+// into this handle (HIP events around each chunk's kernel on each target shard's stream, summed),
+// the maximum over shards, in ms.
+extern "C" int raftsim_diag_clone_ms(raft_sim_t* dst, double* ms) {
+  return diag_ms(dst, ms, &Shard::clone_ms);
 }
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was

@@ -25,6 +25,9 @@
 // The counts a pair's parts need of its node records (req_count, res_count, commit_count) are read
 // once per pair into LDS. The host has checked every record (scatter_host.hpp); the clamps here
 // only keep a record it somehow let through inside its part.
+//
+// The unit's second state writer, clone_kernel (below), is this kernel fed by gather_kernel's reads
+// instead of a record: cluster to cluster on the device ("Cluster clones").
 #include "pack.hpp"
 
 namespace rs {
@@ -125,6 +128,144 @@ hipError_t launch_scatter(const DevSim& S, const void* pairs, uint32_t n,
   hipLaunchKernelGGL(scatter_kernel, pack_grid(n, splits), dim3(PACK_BLOCK), 0, st, S,
                      static_cast<const uint2*>(pairs), n, splits, Y,
                      static_cast<const uint8_t*>(in));
+  return hipGetLastError();
+}
+
+// clone_kernel — cluster state copied on the device (include/raftsim.h, "Cluster clones"): cluster
+// pairs[r].y of the shard Src becomes cluster pairs[r].x of the shard T, and the target is left bit
+// for bit as scatter_kernel leaves it from the record gather_kernel packs of the source, without
+// that record: one read and one write of the state. Src and T may be one shard; the host refuses a
+// cluster that is both read and written, so no pair's source is any pair's target. The launch shape
+// and a workgroup's share of a pair are the two kernels' (pack.hpp), the stride that of the record
+// with every part a scatter needs. Per pair:
+//   - the hot block a word per lane: the cluster's five words, words 5-7 and the pad zero; a node
+//     field through hot_clone (node_codec.hpp: hot_field of node_word, so an owed draw is resolved
+//     with the source's global id and Src's keys, and FL_DRAW is clear); a queue word through
+//     queue_field from the source rings' counts and the arrivals of their first and last messages,
+//     read from the rings;
+//   - the queues 16 bytes per lane: message p from source slot (head + p) mod Q to target slot p,
+//     zero at and past the count;
+//   - the arenas two entries per lane, each side with 16-byte accesses where it can and 8-byte ones
+//     where it cannot (arena_access_bytes; an odd arena_cap gives all four combinations);
+//   - commit_count and the commit-stream rings a word per lane: slot s from slot s where it holds
+//     a kept value, else zero (stream_slot_kept has the derivation).
+// What a pair's parts need per node (QMETA, the rings' end arrivals, commit_count) is read once
+// per pair into LDS.
+__global__ void __launch_bounds__(PACK_BLOCK)
+clone_kernel(const DevSim T, const DevSim Src, const uint2* __restrict__ pairs, uint32_t n,
+             uint32_t splits) {
+  __shared__ uint32_t s_qm[RAFT_MAX_NODES], s_cc[RAFT_MAX_NODES], s_arr[2][RAFT_MAX_NODES],
+      s_tail[2][RAFT_MAX_NODES];
+  const uint32_t N = T.N, Q = T.Q, A = T.A, SC = T.SC, HB = T.HB, tid = threadIdx.x;
+  const uint4 zero4 = make_uint4(0, 0, 0, 0);
+  const DrawKeys dk = {Src.el_base, Src.el_span, Src.key0, Src.key1};
+  const PackLanes ln(splits);
+  const uint32_t first = ln.first, step = ln.step;
+  for (uint32_t r = ln.r0; r < n; r += ln.rstep) {
+    const uint32_t ct = pairs[r].x, cs = pairs[r].y;
+    if (ct >= T.C || cs >= Src.C) continue;              // (the host refuses such a list)
+    __syncthreads();                                     // the pair before is done with the LDS
+    if (tid < N) {
+      const uint32_t qm = hot_node(Src, cs, tid)[HF_QMETA * N], cc = Src.ccount[(size_t)cs * N + tid];
+      s_qm[tid] = qm;
+      s_cc[tid] = cc;
+      if (ln.sp == 0) T.ccount[(size_t)ct * N + tid] = cc;
+#pragma unroll
+      for (int which = 0; which < 2; ++which) {
+        // a queue never exceeds inbox_cap; the clamp keeps a corrupt word inside the ring
+        const uint32_t head = which ? qm_res_head(qm) : qm_req_head(qm);
+        const uint32_t cnt = min(which ? qm_res_cnt(qm) : qm_req_cnt(qm), Q);
+        const uint32_t* const ring = qslots(Src, cs * N + tid, which);
+        const size_t qs = qstride(Src, which);
+        s_arr[which][tid] = cnt ? ring[(head % Q) * qs] : 0u;
+        s_tail[which][tid] = cnt ? ring[((head + cnt - 1) % Q) * qs] : 0u;
+      }
+    }
+    __syncthreads();
+
+    {                                                    // the hot block, a word per lane
+      uint32_t* const hb = hot_cl(T, ct);
+      const uint32_t* const cl = hot_cl(Src, cs);
+      for (uint32_t w = first; w < HB; w += step) {
+        uint32_t v = 0;                                  // words 5-7 (CL_CTERM, CL_CERT) and the pad
+        if (w <= CL_CLIENT_COUNT) {
+          v = cl[w];
+        } else if (w >= HOT_CW) {
+          const uint32_t f = (w - HOT_CW) / N, k = (w - HOT_CW) - f * N;
+          if (hf_is_queue(f)) {
+            const uint32_t qm = s_qm[k];
+            v = queue_field(f, ring_words(0, min(qm_req_cnt(qm), Q), s_arr[0][k], s_tail[0][k]),
+                            ring_words(1, min(qm_res_cnt(qm), Q), s_arr[1][k], s_tail[1][k]));
+          } else if (f < hot_fields(N)) {
+            v = hot_clone(hot_node(Src, cs, k), N, f, Src.goff + cs, k, dk);
+          }
+        }
+        hb[w] = v;
+      }
+    }
+
+    {                                                    // per node REQ then RES, head first
+      const uint32_t total = N * 2 * Q * 2;              // halves of messages
+      for (uint32_t i = first; i < total; i += step) {
+        const QueueElem e = queue_elem(i, Q);
+        const uint32_t qm = s_qm[e.k];
+        const uint32_t head = e.which ? qm_res_head(qm) : qm_req_head(qm);
+        const uint32_t cnt = min(e.which ? qm_res_cnt(qm) : qm_req_cnt(qm), Q);
+        uint4 v = zero4;
+        if (e.p < cnt) {
+          const uint32_t slot = (head + e.p) % Q;
+          v = reinterpret_cast<const uint4*>(qslots(Src, cs * N + e.k, (int)e.which) +
+                                             slot * qstride(Src, (int)e.which))[e.half];
+        }
+        reinterpret_cast<uint4*>(qslots(T, ct * N + e.k, (int)e.which) +
+                                 e.p * qstride(T, (int)e.which))[e.half] = v;
+      }
+    }
+
+    {                                                    // per node the raw arena
+      const uint32_t entries = N * A, chunks = (entries + 1) >> 1;
+      const uint2* const sa = arena_of(Src, cs * N);
+      uint2* const ta = arena_of(T, ct * N);
+      const uint64_t s0 = (uint64_t)cs * N * A, t0 = (uint64_t)ct * N * A;
+      for (uint32_t i = first; i < chunks; i += step) {
+        const uint32_t e = 2 * i;
+        const bool both = e + 1 < entries;
+        uint4 v;
+        if (arena_access_bytes(s0, e, entries) == 16) {
+          v = *reinterpret_cast<const uint4*>(sa + e);
+        } else {
+          const uint2 a = sa[e];
+          const uint2 b = both ? sa[e + 1] : make_uint2(0, 0);
+          v = make_uint4(a.x, a.y, b.x, b.y);
+        }
+        if (arena_access_bytes(t0, e, entries) == 16) {
+          *reinterpret_cast<uint4*>(ta + e) = v;
+        } else {
+          ta[e] = make_uint2(v.x, v.y);
+          if (both) ta[e + 1] = make_uint2(v.z, v.w);
+        }
+      }
+    }
+
+    if (SC) {                                            // per node the ring, slot to slot
+      const uint32_t words = N * SC;
+      for (uint32_t i = first; i < words; i += step) {
+        const uint32_t k = i / SC, s = i - k * SC;
+        T.stream[((size_t)ct * N + k) * SC + s] =
+            stream_slot_kept(s, s_cc[k], SC) ? Src.stream[((size_t)cs * N + k) * SC + s] : 0u;
+      }
+    }
+  }
+}
+
+// Make cluster pairs[i].x of T the state of cluster pairs[i].y of Src (device list, shard-local
+// ids), n pairs. stride: that of the record a scatter needs (it sizes a pair's workgroups).
+hipError_t launch_clone(const DevSim& T, const DevSim& Src, const void* pairs, uint32_t n,
+                        uint64_t stride, hipStream_t st) {
+  if (!n) return hipSuccess;
+  const uint32_t splits = pack_splits(stride);
+  hipLaunchKernelGGL(clone_kernel, pack_grid(n, splits), dim3(PACK_BLOCK), 0, st, T, Src,
+                     static_cast<const uint2*>(pairs), n, splits);
   return hipGetLastError();
 }
 

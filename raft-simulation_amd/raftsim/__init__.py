@@ -15,7 +15,7 @@ from . import _build
 from ._abi import COUNTER_NAMES  # noqa: F401
 from . import _abi
 from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, ClusterPack, GpuBackend,  # noqa: F401
-                       RaftSimError, check_pack_fits, replay_config)
+                       RaftSimError, check_clone_fits, check_pack_fits, replay_config)
 
 PKG_DIR = Path(__file__).resolve().parent.parent          # raft-simulation_amd/
 LIB_PATH = Path(os.environ.get("RAFTSIM_LIB", PKG_DIR / "build" / "libraftsim.so"))
@@ -196,3 +196,67 @@ def _override(cfg, overrides):
         if k not in cfg:
             raise TypeError(f"unknown config field {k!r}")
     return dict(cfg, **overrides)
+
+
+def _ids(xs):
+    return [int(x["cluster"] if isinstance(x, dict) else x) for x in xs]
+
+
+def split_plan(survivors, victims):
+    """The (sources, targets) lists of an importance split (needs no library): victim j is to be
+    overwritten with survivor j % len(survivors), so the survivors' states are spread evenly over
+    the victims. Both take handle-local ids or the record dicts the queries return. Refuses (
+    ValueError) an empty list of survivors, a victim that is also a survivor and a victim named
+    twice; no victims gives two empty lists."""
+    survivors, victims = _ids(survivors), _ids(victims)
+    if not survivors:
+        raise ValueError("split_plan: no survivors")
+    alive, seen = set(survivors), set()
+    for j, v in enumerate(victims):
+        if v in alive:
+            raise ValueError(f"split_plan: victims[{j}] = {v} is also a survivor")
+        if v in seen:
+            raise ValueError(f"split_plan: victims[{j}] = {v} is a victim twice")
+        seen.add(v)
+    return [survivors[j % len(survivors)] for j in range(len(victims))], victims
+
+
+def split(sim, survivors, victims):
+    """Respawn (importance splitting) inside one handle: overwrite the clusters `victims` of `sim`
+    with copies of the clusters `survivors`, as split_plan pairs them, by one clone() on the
+    device. Philox is keyed by the global cluster id, so every copy is an independent future of its
+    survivor from sim's tick on. Returns the plan (sources, targets): the caller keeps the lineage.
+    Violation records, counters and trace `seq` numbers are not state and are not carried: a
+    victim's violation record stays the one of the cluster it was."""
+    sources, targets = split_plan(survivors, victims)
+    sim.clone(sources, targets)
+    return sources, targets
+
+
+def snapshot(sim, **overrides):
+    """A new Simulator on the same GPU holding the state of every cluster of `sim` at sim.tick: a
+    device-resident checkpoint, filled by one clone() with nothing passing through host memory. It
+    has sim's config (`overrides` replace any field, as in resume(): with the same seed, timers,
+    rates and cluster_offset it continues bit-exactly as sim does). Violation records, counters
+    and trace `seq` numbers are not state and are not carried: the snapshot's start empty."""
+    cfg = _override({f: getattr(sim.config, f) for f, _ in _abi.Config._fields_}, overrides)
+    snap = Simulator(**cfg)
+    try:
+        snap.set_tick(sim.tick)
+        snap.clone(range(sim.C), range(sim.C), source=sim)
+    except Exception:
+        snap.close()
+        raise
+    return snap
+
+
+def rollback(sim, snap):
+    """Take `sim` back to the snapshot `snap` (snapshot(sim) at an earlier tick): every cluster is
+    cloned back on the device and sim's clock is set to snap.tick. sim then runs the window again
+    exactly as it did the first time (a snapshot of sim's own config continues bit-exactly).
+    Violation records, counters and trace `seq` numbers are not state and are not carried: sim's
+    keep what the abandoned window added."""
+    if sim.C != snap.C:
+        raise ValueError(f"rollback: the snapshot holds {snap.C} clusters, the handle {sim.C}")
+    sim.clone(range(snap.C), range(sim.C), source=snap)
+    sim.set_tick(snap.tick)

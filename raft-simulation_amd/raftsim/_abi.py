@@ -317,6 +317,16 @@ SCATTER_SYMBOLS = ["raft_scatter_" + n for n in _SCATTER_SIGS]
 SCATTER_PARTS = ("cluster", "nodes", "queues", "arenas")
 
 
+# Cluster state copied on the device (include/raftsim.h, "Cluster clones"): (dst, targets, src,
+# sources, n), under a prefix of its own like the scatter.
+_CLONE_SIGS = {
+    "write": (C.c_int64, [C.c_void_p, P(C.c_uint32), C.c_void_p, P(C.c_uint32), C.c_uint32]),
+}
+CLONE_SYMBOLS = ["raft_clone_" + n for n in _CLONE_SIGS]
+# the config fields two handles must share for a clone between them (arena_cap: the effective one)
+CLONE_SHAPE = ("nodes", "inbox_cap", "log_cap", "arena_cap", "commit_stream_cap")
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

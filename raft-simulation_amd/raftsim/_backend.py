@@ -452,6 +452,7 @@ class GpuBackend(Backend):
         self._audit = _abi.bind(self._lib, "raft_audit_", sigs=_abi._AUDIT_SIGS)
         self._gather = _abi.bind(self._lib, "raft_gather_", sigs=_abi._GATHER_SIGS)
         self._scatter = _abi.bind(self._lib, "raft_scatter_", sigs=_abi._SCATTER_SIGS)
+        self._clone = _abi.bind(self._lib, "raft_clone_", sigs=_abi._CLONE_SIGS)
 
     # -- what the three device-side queries share ------------------------------------------------
     @staticmethod
@@ -690,6 +691,50 @@ class GpuBackend(Backend):
         """Diagnostic: device time (HIP events) of the last scatter()'s kernels."""
         return self._diag_ms("raftsim_diag_scatter_ms")
 
+    # -- cluster clones (include/raftsim.h, "Cluster clones") ------------------------------------
+    def clone(self, sources, targets, source=None):
+        """Make cluster targets[i] of this handle the state of cluster sources[i] of `source`
+        (default: this handle) on the device (raft_clone_write), with no pack in host memory:
+        returns the number of clusters written. Both lists hold handle-local ids or the record
+        dicts violations(), select() and audit_select() return (their "cluster" key is used), in
+        any order; a source may be named any number of times (K targets of one source are K
+        futures of that state: Philox is keyed by the global cluster id), a target once, and
+        within one handle no cluster may be both. The target is what
+        scatter(source.gather(sources)) leaves: exact deadlines, no steady certificate. The two
+        handles must have the same nodes, inbox_cap, log_cap, arena_cap and commit_stream_cap and
+        live on one GPU: ValueError names the field or the position. Neither clock is touched
+        (set_tick does that); violation records, counters and trace `seq` numbers are not state
+        and are not carried: the target's stay as they are. All or nothing: a refused call
+        (RaftSimError naming the first offending position) wrote nothing."""
+        src = self if source is None else source
+        if not isinstance(src, GpuBackend):
+            raise TypeError("clone: the source must be a handle of libraftsim.so")
+        check_clone_fits(self.config, src.config)
+
+        def index_list(xs, name, bound):
+            if not isinstance(xs, np.ndarray):
+                xs = [int(x["cluster"] if isinstance(x, dict) else x) for x in xs]
+            a = np.asarray(xs, dtype=np.int64).reshape(-1)
+            out = np.flatnonzero((a < 0) | (a >= bound))
+            if out.size:
+                raise ValueError(f"{name}[{out[0]}] = {a[out[0]]} is outside the handle's {bound}")
+            return np.ascontiguousarray(a, dtype=np.uint32)
+
+        src_idx = index_list(sources, "sources", src.C)
+        tgt_idx = index_list(targets, "targets", self.C)
+        if src_idx.size != tgt_idx.size:
+            raise ValueError(f"{src_idx.size} sources for {tgt_idx.size} targets")
+        u32p = C.POINTER(C.c_uint32)
+        self.host_written = True
+        return self._check(int(self._clone["write"](
+            self._h, tgt_idx.ctypes.data_as(u32p), src._h, src_idx.ctypes.data_as(u32p),
+            tgt_idx.size)))
+
+    def last_clone_ms(self):
+        """Diagnostic: device time (HIP events) of the kernels of the last clone() into this
+        handle."""
+        return self._diag_ms("raftsim_diag_clone_ms")
+
     def replay_config(self, cluster, **overrides):
         """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster
         `cluster` of this one alone: Philox is keyed by the global cluster id, so n_clusters=1 at
@@ -711,6 +756,21 @@ def check_pack_fits(config, pack, who):
         raise ValueError(f"{who}: the handle's nodes, inbox_cap, log_cap, arena_cap, "
                          f"commit_stream_cap {mine} are not the pack's "
                          f"{(pack.N, pack.Q, pack.L, pack.A, pack.SC)}")
+
+
+def check_clone_fits(config, source_config):
+    """What two handles must share for a clone between them (needs no library): nodes, inbox_cap,
+    log_cap, the effective arena_cap and commit_stream_cap. ValueError names the first that
+    differs."""
+    def shape(c):
+        return {f: (c.arena_cap or 4 * c.log_cap) if f == "arena_cap" else getattr(c, f)
+                for f in _abi.CLONE_SHAPE}
+
+    mine, theirs = shape(config), shape(source_config)
+    for f in _abi.CLONE_SHAPE:
+        if mine[f] != theirs[f]:
+            raise ValueError(f"clone: the handles differ in {f}: the target's is {mine[f]}, "
+                             f"the source's {theirs[f]}")
 
 
 def replay_config(config, cluster, **overrides):
