@@ -110,13 +110,12 @@ _cache = {}
 def oracle_at(cfg, ticks):
     """[(census, records)] of an oracle run of cfg from init-node, one per checkpoint of the
     increasing tuple `ticks`. Computed once per argument set and shared between the tests."""
-    import helpers
+    import pairing
 
     key = (tuple(sorted(cfg.items())), tuple(ticks))
     if key not in _cache:
         out = []
-        with helpers.oracle(**cfg) as h:
-            helpers.oracle_threads(h, helpers.cpu_threads())
+        with pairing.oracle(cfg) as h:
             for t in ticks:
                 h.step(t - h.tick)
                 out.append(of_backend(h))

@@ -109,6 +109,13 @@ def cpu_threads():
     return max(1, n)
 
 
+def client_set_into(be, cluster, node, value):
+    """Append a client-set (SIM_SPEC §3, server.clj:12) to a node's REQ queue, arriving now."""
+    q = [list(m) for m in be.read_queue(cluster, node, 0)]
+    arr = max([be.tick] + [m[0] for m in q])
+    be.write_queue(cluster, node, 0, q + [[arr, 3, 0, value, 0, 0, 0, 0]])
+
+
 BURST_GATE = 2 ** 28 - 1      # the burst engine runs in launches that end at or before this tick
 
 
@@ -185,22 +192,24 @@ def burst_witness(cfg, ticks=20000, stride=7, clusters=16, tick0=0, setup=None):
     return w, counters
 
 
-def describe_cluster_diff(a, b, cluster):
-    """Human-readable differences between cluster `cluster` of two backends."""
+def describe_cluster_diff(a, b, cluster, cluster_b=None):
+    """Human-readable differences between cluster `cluster` of a and the same cluster of b (or
+    its cluster `cluster_b`, where b holds a slice of a's clusters)."""
     lines = []
-    ra, rb = a.read_nodes(cluster, 1), b.read_nodes(cluster, 1)
+    cb = cluster if cluster_b is None else cluster_b
+    ra, rb = a.read_nodes(cluster, 1), b.read_nodes(cb, 1)
     for i, (x, y) in enumerate(zip(ra, rb)):
         for f in x:
             if x[f] != y[f]:
                 lines.append(f"  node {i + 1} {f}: {x[f]} != {y[f]}")
         for which in (0, 1):
-            qa, qb = a.read_queue(cluster, i + 1, which), b.read_queue(cluster, i + 1, which)
+            qa, qb = a.read_queue(cluster, i + 1, which), b.read_queue(cb, i + 1, which)
             if qa != qb:
                 lines.append(f"  node {i + 1} queue {which}: {qa} != {qb}")
-        la, lb = a.log(cluster, i + 1), b.log(cluster, i + 1)
+        la, lb = a.log(cluster, i + 1), b.log(cb, i + 1)
         if la != lb:
             lines.append(f"  node {i + 1} log: {la[:12]}... != {lb[:12]}...")
-    ha, hb = a.read_clusters(cluster, 1), b.read_clusters(cluster, 1)
+    ha, hb = a.read_clusters(cluster, 1), b.read_clusters(cb, 1)
     if ha != hb:
         lines.append(f"  cluster record {ha} != {hb}")
     return "\n".join(lines)
@@ -218,5 +227,5 @@ def bisect_divergence(cfg, g, max_ticks, make_a, make_b):
             return (f"cluster {g} first diverges at tick {t}:\n"
                     + describe_cluster_diff(a, b, 0)
                     + (f"\n  state before tick {t} (a):\n{prev}" if prev else ""))
-        prev = "\n".join(f"    {r}" for r in a.read_nodes(0, 1)) if t % 1 == 0 else prev
+        prev = "\n".join(f"    {r}" for r in a.read_nodes(0, 1))
     return f"cluster {g}: no divergence in {max_ticks} single-tick steps (launch-size effect?)"

@@ -16,6 +16,7 @@ deadline is overdue and all N timers fire together at T0 (a legal state). The th
 import numpy as np
 
 import helpers
+import pairing
 import pyref
 
 LOW = 50_000
@@ -106,20 +107,15 @@ def setup_for(cfg, T0):
     return setup
 
 
-def same_digests(g, r, what):
-    assert g.tick == r.tick, (what, g.tick, r.tick)
-    bad = np.nonzero(g.digest() != r.digest())[0]
-    assert not len(bad), (f"{what} (tick {r.tick}): {len(bad)} of {r.C} clusters differ, first "
-                          f"{bad[0]}:\n" + helpers.describe_cluster_diff(g, r, int(bad[0])))
+def oracle(**cfg):
+    """`make` for start(): the oracle handle of cfg on every CPU."""
+    return pairing.oracle(cfg)
 
 
-def run_pair(g, r, chunks):
-    """Step both handles through `chunks` (tick counts); after each the clocks and every
-    cluster's digest are equal, or the first differing cluster is described."""
-    for i, n in enumerate(chunks):
-        g.step(n)
-        r.step(n)
-        same_digests(g, r, f"chunk {i} of {n} ticks")
+def pair(cfg, T0):
+    """(g, r): the GPU handle and the oracle handle of cfg, both moved to T0 by start() and closed
+    on exit."""
+    return pairing.closing(start(helpers.gpu, cfg, T0), start(oracle, cfg, T0))
 
 
 def refused_at_the_end(h, cfg):

@@ -7,7 +7,7 @@ A cluster on the fixed point's schedule has its first heartbeat of a launch at t
 K1 = R / P + 1 and rho = R % P, it runs K1 whole rounds when delta <= rho and K1 - 1 otherwise.
 Every function that steps takes a list of backends and does the same to each, so the GPU test runs
 it on (gpu, oracle) and the witness on (oracle,)."""
-from test_gpu_steady_line0 import cut_cfg
+from cases import cut_cfg
 
 C_BAND = 199
 # (nodes, d) -> clusters, where 199 do not put a cluster on both sides of every rho below

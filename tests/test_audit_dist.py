@@ -1,16 +1,9 @@
 """dist.reduce_audit on CPU: gloo, world_size 2 and 1. Each rank takes the audit of its cluster
 shard (tests/audit_oracle.py on the oracle backend, the dict Simulator.audit returns) and the
 ranks all-reduce it; the result must equal the audit of one process holding every cluster."""
-import json
-import os
-import socket
-import sys
-from pathlib import Path
-
-import torch.multiprocessing as mp
-
 import audit_oracle as ao
-from test_gpu_parity import CASES
+import gloo
+from cases import CASES
 
 # few clusters with diverged and identical logs and common prefixes of several lengths
 CFG = dict(CASES["spec_arena_odd"])
@@ -21,26 +14,12 @@ def _shard_audit(off, cnt):
     return ao.oracle_at(dict(CFG, n_clusters=cnt, cluster_offset=off), (TICKS,))[0][0]
 
 
-def _worker(rank, world, port, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    root = Path(__file__).resolve().parent.parent
-    sys.path[:0] = [str(root / "raft-simulation_amd"), str(root / "tests"), str(root / "oracle")]
-    import torch.distributed as dist
+def _worker(rank, world):
     from raftsim import dist as rdist
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    off, cnt = rdist.shard(TOTAL, rank, world)
-    mine = _shard_audit(off, cnt)
+    mine = _shard_audit(*rdist.shard(TOTAL, rank, world))
     red = rdist.reduce_audit(mine)
-    if rank == 0:
-        Path(out).write_text(json.dumps({"reduced": red, "keys": [list(mine), list(red)]}))
-    dist.destroy_process_group()
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+    return {"reduced": red, "keys": [list(mine), list(red)]}
 
 
 def test_sharded_audit_equals_single_process(tmp_path):
@@ -53,9 +32,7 @@ def test_sharded_audit_equals_single_process(tmp_path):
     assert whole["commit_diverge_index_min"] is None           # a minimum nobody has stays None
     assert any(h[k] != whole[k] for h in halves for k in ("agree_max", "agree_min"))
     for world in (2, 1):
-        out = tmp_path / f"r{world}.json"
-        mp.spawn(_worker, args=(world, _free_port(), str(out)), nprocs=world, join=True)
-        got = json.loads(out.read_text())
+        got = gloo.spawn(_worker, world, tmp_path / f"r{world}.json")
         assert got["reduced"] == whole, world
         assert got["keys"][0] == got["keys"][1] == list(whole)       # the dict keeps its order
     assert whole["entries"] == sum(h["entries"] for h in halves)

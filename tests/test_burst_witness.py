@@ -16,7 +16,8 @@ test_gpu_burst_engine.py checks its own precondition on the oracle inside the te
 import pytest
 
 import helpers
-from test_gpu_parity import B4, CASES, FAST
+import pairing
+from cases import CASES, GATE_CFG, GATE_T0, GATE_TICKS, gate_setup
 
 #                          eligible entered broke longer halted
 MEASURED = {
@@ -64,8 +65,7 @@ FULL_MEASURED = {
 @pytest.mark.parametrize("name", list(FULL_MEASURED))
 def test_full_case_counters(name):
     cfg = CASES[name]
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
+    r = pairing.oracle(cfg)
     r.step(20000)
     full = r.counters()
     print(name, {k: v for k, v in full.items() if v})
@@ -76,20 +76,6 @@ def test_full_case_counters(name):
     if name == "burst_arena_odd_n7":
         assert cfg["arena_cap"] % 8 and cfg["arena_cap"] > 2 * cfg["log_cap"]
     r.close()
-
-
-# The 2^28 gate (test_gpu_burst_engine.py::test_gpu_burst_gate_2_28): the engine packs arrivals in
-# 28 bits and runs only in launches that end at or before tick 2^28 - 1.
-GATE_T0 = 2 ** 28 - 15000
-GATE_TICKS = 24000
-GATE_CFG = dict(n_clusters=256, nodes=7, seed=131, ticks_per_launch=2500, drop_ppm=20000, dmin=1,
-                dmax=8, **B4, **FAST)
-
-
-def gate_setup(be):
-    """After set_tick no client-set is ever injected unless the cursors are written too."""
-    be.write_clusters(0, [dict(hwm=(0, 0, 0), client_next=GATE_T0 + 1500 + 3 * i, client_count=0)
-                          for i in range(be.C)])
 
 
 def test_gate_case_has_engine_states_on_both_sides():

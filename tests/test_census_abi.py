@@ -10,9 +10,9 @@ import census_oracle as co
 import helpers
 import hostprog
 import raftsim
+from cases import CASES
 from hostprog import HEADER, ROOT
 from raftsim import _abi
-from test_gpu_parity import CASES
 
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 

@@ -1,16 +1,9 @@
 """dist.reduce_census on CPU: gloo, world_size 2 and 1. Each rank takes the census of its cluster
 shard (tests/census_oracle.py on the oracle backend, the dict Simulator.census returns) and the
 ranks all-reduce it; the result must equal the census of one process holding every cluster."""
-import json
-import os
-import socket
-import sys
-from pathlib import Path
-
-import torch.multiprocessing as mp
-
 import census_oracle as co
-from test_gpu_parity import CASES
+import gloo
+from cases import CASES
 
 # few clusters with every kind of node: halts, leaders, candidates, queued messages
 CFG = dict(CASES["arena_odd"])
@@ -21,26 +14,12 @@ def _shard_census(off, cnt):
     return co.oracle_at(dict(CFG, n_clusters=cnt, cluster_offset=off), (TICKS,))[0][0]
 
 
-def _worker(rank, world, port, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    root = Path(__file__).resolve().parent.parent
-    sys.path[:0] = [str(root / "raft-simulation_amd"), str(root / "tests"), str(root / "oracle")]
-    import torch.distributed as dist
+def _worker(rank, world):
     from raftsim import dist as rdist
 
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    off, cnt = rdist.shard(TOTAL, rank, world)
-    mine = _shard_census(off, cnt)
+    mine = _shard_census(*rdist.shard(TOTAL, rank, world))
     red = rdist.reduce_census(mine)
-    if rank == 0:
-        Path(out).write_text(json.dumps({"reduced": red, "keys": [list(mine), list(red)]}))
-    dist.destroy_process_group()
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+    return {"reduced": red, "keys": [list(mine), list(red)]}
 
 
 def test_sharded_census_equals_single_process(tmp_path):
@@ -50,9 +29,7 @@ def test_sharded_census_equals_single_process(tmp_path):
     assert whole["by_class"]["halted"] and whole["by_class"]["one_leader"]
     assert whole["term_min"] < whole["term_max"] and whole["req_queued"] and whole["hwm_max"]
     for world in (2, 1):
-        out = tmp_path / f"r{world}.json"
-        mp.spawn(_worker, args=(world, _free_port(), str(out)), nprocs=world, join=True)
-        got = json.loads(out.read_text())
+        got = gloo.spawn(_worker, world, tmp_path / f"r{world}.json")
         assert got["reduced"] == whole, world
         assert got["keys"][0] == got["keys"][1] == list(whole)       # the dict keeps its order
     halves = [_shard_census(0, 30), _shard_census(30, 31)]

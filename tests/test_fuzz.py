@@ -3,11 +3,11 @@ C oracle == GPU kernel (gpu). Each state runs 8 ticks; every field, queue, log a
 agree."""
 import random
 
-import numpy as np
 import pytest
 
 import fuzz
 import helpers
+import pairing
 import scenarios
 
 TICKS = 8
@@ -37,30 +37,18 @@ def test_fuzz_gpu_equals_oracle(seed):
     rng = random.Random(5000 + seed)
     cfg = fuzz.random_config(rng)
     scns = [fuzz.random_scenario(rng, cfg) for _ in range(200)]
-    g = fuzz.load_batch(helpers.gpu, cfg, scns)
-    r = fuzz.load_batch(helpers.oracle, cfg, scns)
-    assert np.array_equal(g.digest(), r.digest()), "state load differs"
-    for _ in range(TICKS):
-        g.step(1)
-        r.step(1)
-        dg, dr = g.digest(), r.digest()
-        bad = np.nonzero(dg != dr)[0]
-        assert not len(bad), (f"tick {g.tick - 1}: {len(bad)} clusters differ; first {bad[0]}\n"
-                              + helpers.describe_cluster_diff(g, r, int(bad[0])))
-    assert g.counters() == r.counters()
+    with pairing.closing(fuzz.load_batch(helpers.gpu, cfg, scns),
+                         fuzz.load_batch(helpers.oracle, cfg, scns)) as (g, r):
+        pairing.same(g, r, "state load")
+        pairing.run(g, r, [1] * TICKS, "tick")
+        pairing.same_counters(g, r)
 
 
 def _gpu_vs_oracle_multi_tick(cfg, scns, steps):
-    g = fuzz.load_batch(helpers.gpu, cfg, scns)
-    r = fuzz.load_batch(helpers.oracle, cfg, scns)
-    for n in steps:
-        g.step(n)
-        r.step(n)
-        dg, dr = g.digest(), r.digest()
-        bad = np.nonzero(dg != dr)[0]
-        assert not len(bad), (f"after tick {g.tick}: {len(bad)} clusters differ; first {bad[0]}\n"
-                              + helpers.describe_cluster_diff(g, r, int(bad[0])))
-    assert g.counters() == r.counters()
+    with pairing.closing(fuzz.load_batch(helpers.gpu, cfg, scns),
+                         fuzz.load_batch(helpers.oracle, cfg, scns)) as (g, r):
+        pairing.run(g, r, steps, "launch")
+        pairing.same_counters(g, r)
 
 
 @pytest.mark.gpu

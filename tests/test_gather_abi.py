@@ -12,31 +12,14 @@ import pytest
 import gather_mirror as gm
 import helpers
 import hostprog
+import pairing
 import raftsim
+from cases import CASES, GPU_CASES, ROUNDTRIP
 from hostprog import HEADER, ROOT
 from raftsim import ClusterPack, _abi
-from test_gpu_parity import CASES, FAULTS
 
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 NONE64 = 2 ** 64 - 1
-
-# The cases tests/test_gpu_gather.py runs for parity: (config, ticks). Chosen here, on the oracle,
-# so that the witnesses below hold.
-GPU_CASES = {
-    "arena_odd": (dict(CASES["arena_odd"], n_clusters=96), 6000),
-    "burst_arena_odd_n7": (dict(CASES["burst_arena_odd_n7"], n_clusters=64), 6000),
-    "n2": (dict(CASES["n2"], n_clusters=96), 20000),
-    "c4_n9": (dict(CASES["c4_n9"], n_clusters=64), 20000),
-    "spec_c3": (dict(CASES["spec_c3"], n_clusters=96, commit_stream_cap=8), 20000),
-}
-ROUNDTRIP = dict(n_clusters=64, nodes=5, seed=3, client_ppm=3000, log_cap=64, **FAULTS)
-
-
-def run_oracle(cfg, ticks):
-    h = helpers.oracle(**cfg)
-    helpers.oracle_threads(h, min(helpers.cpu_threads(), 8))
-    h.step(ticks)
-    return h
 
 
 def test_layouts_match_the_c_compiler(tmp_path):
@@ -166,7 +149,7 @@ def test_clojure_facade_names_the_entry_points():
 def test_python_refusals():
     with pytest.raises(ValueError, match="unknown pack part"):
         raftsim.GpuBackend._mask(("trace",), _abi.GATHER_PARTS, "pack part")
-    h = run_oracle(dict(ROUNDTRIP, n_clusters=2), 100)
+    h = pairing.oracle(dict(ROUNDTRIP, n_clusters=2), threads=8, ticks=100)
     with pytest.raises(ValueError, match="not len"):
         ClusterPack({f: getattr(h.config, f) for f, _ in _abi.Config._fields_}, 0, [0],
                     gm.layout_of(h), np.zeros(3, dtype=np.uint8))
@@ -189,7 +172,7 @@ def test_python_refusals():
         with pytest.raises(ValueError, match="log_cap"):
             other.restore_cluster(pack, 0)
     # a stream-keeping config needs the streams
-    s = run_oracle(dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4), 100)
+    s = pairing.oracle(dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4), threads=8, ticks=100)
     with helpers.oracle(**dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4)) as one:
         with pytest.raises(ValueError, match="'streams'"):
             one.restore_cluster(gm.pack_of(s, [0], gm.PARTS[:-1]), 0)
@@ -202,7 +185,7 @@ PACK_CASES = {"arena_odd": dict(CASES["arena_odd"], n_clusters=32),
 @pytest.mark.parametrize("name", list(PACK_CASES))
 def test_cluster_pack_over_the_mirror(name, tmp_path):
     cfg = PACK_CASES[name]
-    h = run_oracle(cfg, 6000)
+    h = pairing.oracle(cfg, threads=8, ticks=6000)
     order = list(range(31, -1, -1)) + [5, 5]
     pack = gm.pack_of(h, order)
     assert len(pack) == 34 and pack.tick == 6000 and pack.parts == gm.PARTS
@@ -246,7 +229,7 @@ def test_cluster_pack_over_the_mirror(name, tmp_path):
     (dict(CASES["spec_c3"], n_clusters=64, commit_stream_cap=8), 15000),
 ], ids=["roundtrip", "spec_c3_streams"])
 def test_restore_continues_bit_exactly_on_the_oracle(cfg, t0):
-    src = run_oracle(cfg, t0)
+    src = pairing.oracle(cfg, threads=8, ticks=t0)
     picks = [0, 31, 63]
     pack = gm.pack_of(src, picks)
     if cfg.get("commit_stream_cap"):
@@ -277,7 +260,7 @@ def test_witnesses_the_gpu_cases_reach_the_states():
     seen = {}
     for name, (cfg, ticks) in GPU_CASES.items():
         assert cfg["n_clusters"] <= 96 and 6000 <= ticks <= 20000
-        h = run_oracle(cfg, ticks)
+        h = pairing.oracle(cfg, threads=8, ticks=ticks)
         N, A, SC = cfg["nodes"], h.config.arena_cap or 4 * h.config.log_cap, \
             h.config.commit_stream_cap
         recs = h.read_nodes()

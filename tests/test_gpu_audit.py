@@ -11,15 +11,10 @@ import pytest
 import audit_oracle as ao
 import audit_shapes
 import helpers
+from cases import CASES, PARITY, cfg_of
 from raftsim import _abi, dist
-from test_gpu_census import PARITY
-from test_gpu_parity import CASES
 
 pytestmark = pytest.mark.gpu
-
-
-def cfg_of(name, n, **extra):
-    return dict(CASES[name], n_clusters=n, **extra)
 
 
 def check_identities(s):

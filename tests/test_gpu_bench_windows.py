@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import helpers
+import pairing
 from raftsim import COUNTER_NAMES as BENCH_COUNTERS
 from raftsim import dist as rdist
 
@@ -35,22 +36,12 @@ BENCH = _bench()
 STEPS, WARMUP = 20, 5          # the driver's fixed command; bench.py's defaults (test_bench_contract)
 
 
-def _oracle(**cfg):
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r, True)
-    return r
-
-
 def _check_slices(g, cfg, total, part, when):
     """First, middle and last `part` clusters of the GPU handle vs the oracle run alone on each."""
     for lo in (0, (total // 2) - part // 2, total - part):
-        r = _oracle(n_clusters=part, cluster_offset=lo, **cfg)
-        r.step(when)
-        bad = np.nonzero(g.digest(lo, part) != r.digest())[0]
-        assert not len(bad), (f"after {when} ticks: {len(bad)} clusters of [{lo}, {lo + part}) "
-                              f"differ; first {lo + int(bad[0])}")
-        r.close()
+        sub = dict(cfg, n_clusters=part, cluster_offset=lo)
+        with pairing.oracle(sub, ticks=when, idle_skip=True) as r:
+            pairing.same(g, r, f"clusters [{lo}, {lo + part})", lo=lo)
 
 
 def test_gpu_c2_bench_window():
@@ -59,18 +50,17 @@ def test_gpu_c2_bench_window():
     the oracle after the warm-up and at the end, every counter equal."""
     spec = BENCH.WORKLOADS["c2"]
     cfg = dict(n_clusters=spec["clusters"], **spec["cfg"])
-    g, r = helpers.gpu(**cfg), _oracle(**cfg)
-    for _ in range(WARMUP):
-        g.step(TICKS)
-    r.step(WARMUP * TICKS)
-    assert np.array_equal(g.digest(), r.digest())
-    for _ in range(STEPS):
-        g.step_async(TICKS)
-    g.sync()
-    r.step(STEPS * TICKS)
-    assert g.diag_last_bails() == 0
-    assert np.array_equal(g.digest(), r.digest())
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg, idle_skip=True) as (g, r):
+        for _ in range(WARMUP):
+            g.step(TICKS)
+        r.step(WARMUP * TICKS)
+        pairing.same(g, r, "after the warm-up")
+        for _ in range(STEPS):
+            g.step_async(TICKS)
+        g.sync()
+        r.step(STEPS * TICKS)
+        assert g.diag_last_bails() == 0
+        pairing.same(g, r, "at the end", counters=True)
 
 
 @pytest.mark.parametrize("name", ["c3", "c3_spec"])
@@ -125,14 +115,12 @@ def test_gpu_c5_time_to_violation_bit_exact():
     digests of every cluster."""
     spec = BENCH.WORKLOADS["c5"]
     cfg = dict(n_clusters=spec["clusters"], **spec["cfg"])
-    g = helpers.gpu(**cfg)
-    fv, ticks, _ = rdist.first_violation_search(g, spec["chunk"], spec["max_ticks"])
-    assert fv is not None
-    r = _oracle(**cfg)
-    cfv, cticks, _ = rdist.first_violation_search(r, spec["chunk"], ticks)
-    assert (cfv, cticks) == (fv, ticks)
-    assert np.array_equal(g.digest(), r.digest())
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg, idle_skip=True) as (g, r):
+        fv, ticks, _ = rdist.first_violation_search(g, spec["chunk"], spec["max_ticks"])
+        assert fv is not None
+        cfv, cticks, _ = rdist.first_violation_search(r, spec["chunk"], ticks)
+        assert (cfv, cticks) == (fv, ticks)
+        pairing.same(g, r, "at the violation", counters=True)
 
 
 def test_gpu_bench_line_is_one_parseable_line(tmp_path):
@@ -189,8 +177,8 @@ def test_gpu_plain_bench_run_times_the_headline_alone_and_dumps_it(tmp_path):
     assert not list(tmp_path.glob("*.json"))
 
     spec = BENCH.WORKLOADS["c2"]
-    r = _oracle(n_clusters=clusters, **spec["cfg"])
-    r.step((warmup + steps) * TICKS)
+    r = pairing.oracle(dict(spec["cfg"], n_clusters=clusters), ticks=(warmup + steps) * TICKS,
+                       idle_skip=True)
     files = {f.name: np.load(f) for f in dump.iterdir()}
     assert set(files) == {"digest.npy", "counters.npy", "nodes.npy", "node_clusters.npy"}
     assert all(a.dtype == np.float64 for a in files.values())

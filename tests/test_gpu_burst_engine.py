@@ -7,27 +7,10 @@ import numpy as np
 import pytest
 
 import helpers
-import test_burst_witness as witness
-from test_gpu_parity import B4, CASES, FAST
+import pairing
+from cases import B4, CASES, FAST, GATE_CFG, GATE_T0, GATE_TICKS, gate_setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _pair(cfg):
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    return g, r
-
-
-def _step_and_compare(g, r, n):
-    g.step(n)
-    r.step(n)
-    assert g.tick == r.tick
-    bad = np.nonzero(g.digest() != r.digest())[0]
-    if len(bad):
-        c = int(bad[0])
-        pytest.fail(f"{len(bad)} clusters differ at tick {g.tick}; first {c}\n"
-                    + helpers.describe_cluster_diff(g, r, c))
 
 
 def test_gpu_burst_gate_2_28():
@@ -36,20 +19,15 @@ def test_gpu_burst_gate_2_28():
     mild faults from 15,000 ticks before the gate to 9,000 past it, digest-equal to the oracle
     after every 2,500-tick launch and counter-equal at the end. The oracle alone shows 5489 / 8936
     engine-eligible samples below / above the gate (test_burst_witness.py)."""
-    cfg, T0 = witness.GATE_CFG, witness.GATE_T0
-    g, r = _pair(cfg)
-    for be in (g, r):
-        be.set_tick(T0)
-        witness.gate_setup(be)
-    done = 0
-    while done < witness.GATE_TICKS:
-        n = min(2500, witness.GATE_TICKS - done)
-        _step_and_compare(g, r, n)
-        done += n
-    assert g.tick == T0 + witness.GATE_TICKS > 2 ** 28
-    cg = g.counters()
-    assert cg == r.counters()
-    assert cg["client_injected"] > 0 and cg["payload_max"] >= 500 and cg["dropped"] > 0
+    cfg, T0 = GATE_CFG, GATE_T0
+    with pairing.pair(cfg) as (g, r):
+        for be in (g, r):
+            be.set_tick(T0)
+            gate_setup(be)
+        pairing.run(g, r, pairing.chunks(GATE_TICKS, 2500), "launch")
+        assert g.tick == T0 + GATE_TICKS > 2 ** 28
+        cg = pairing.same_counters(g, r)
+        assert cg["client_injected"] > 0 and cg["payload_max"] >= 500 and cg["dropped"] > 0
 
 
 HOST_CFG = dict(n_clusters=192, nodes=7, seed=141, ticks_per_launch=1000, **B4, **FAST)
@@ -106,44 +84,43 @@ def test_gpu_burst_host_written_leader_messages(schedule):
     entered, where the hop count is not read, so the 15- and 16-hop variants check only that
     nothing else goes wrong with them."""
     cfg = dict(HOST_CFG, schedule=schedule)
-    g, r = _pair(cfg)
-    _step_and_compare(g, r, HOST_STOP)
-    N, C, tick = cfg["nodes"], cfg["n_clusters"], r.tick
-    recs, cl = r.read_nodes(), r.read_clusters()
+    with pairing.pair(cfg) as (g, r):
+        pairing.step(g, r, HOST_STOP)
+        N, C, tick = cfg["nodes"], cfg["n_clusters"], r.tick
+        recs, cl = r.read_nodes(), r.read_clusters()
 
-    def quiet(c):
-        """An idle leader and followers with nothing to do until 16 ticks into the burst."""
-        nodes, cnext = recs[c * N:(c + 1) * N], cl[c]["client_next"]
-        lk = helpers.burst_leader(nodes, tick)
-        return (lk is not None and nodes[lk]["req_count"] == 0 and tick < cnext < tick + 16
-                and all(n["deadline"] > cnext + 16 for n in nodes if not n["fault"]))
+        def quiet(c):
+            """An idle leader and followers with nothing to do until 16 ticks into the burst."""
+            nodes, cnext = recs[c * N:(c + 1) * N], cl[c]["client_next"]
+            lk = helpers.burst_leader(nodes, tick)
+            return (lk is not None and nodes[lk]["req_count"] == 0 and tick < cnext < tick + 16
+                    and all(n["deadline"] > cnext + 16 for n in nodes if not n["fault"]))
 
-    waves = [w for w in range(C // CPW) if all(quiet(c) for c in range(CPW * w, CPW * w + CPW))]
-    assert len(waves) >= 7, waves      # measured on the oracle: 9 of 21 waves, 177 quiet clusters
-    targets = []
-    for v, w in enumerate(waves[:7]):
-        for c in range(CPW * w, CPW * w + (1 if v == 6 else 2)):
-            leader = 1 + helpers.burst_leader(recs[c * N:(c + 1) * N], tick)
-            name, msgs = _host_messages(tick, cl[c]["client_next"], leader, N)[v]
-            targets.append((name, c, leader))
-            for be in (g, r):
-                be.write_queue(c, leader, 0, msgs)
-    assert len(targets) == 13 and targets[-1][0] == "two"
-    for name, c, leader in targets:
-        assert g.read_queue(c, leader, 0) == r.read_queue(c, leader, 0), name
-    assert np.array_equal(g.digest(), r.digest())
-    before = r.counters()
-    for n in (1000, 1000, 1000, 37):
-        _step_and_compare(g, r, n)
-    cg = g.counters()
-    assert cg == r.counters()
-    for k in ("client_injected", "redirects", "entries_appended", "ev_rv"):    # the burst ran
-        assert cg[k] > before[k], k
-    for name, c, leader in targets:                                   # the written values' fate
-        log = r.log(c, leader)
-        assert g.log(c, leader) == log, name
-        if name == "future":            # appended behind the burst's first client-set
-            assert 9004 in [v for _, v in log[1:]], log[:8]
+        waves = [w for w in range(C // CPW)
+                 if all(quiet(c) for c in range(CPW * w, CPW * w + CPW))]
+        assert len(waves) >= 7, waves  # measured on the oracle: 9 of 21 waves, 177 quiet clusters
+        targets = []
+        for v, w in enumerate(waves[:7]):
+            for c in range(CPW * w, CPW * w + (1 if v == 6 else 2)):
+                leader = 1 + helpers.burst_leader(recs[c * N:(c + 1) * N], tick)
+                name, msgs = _host_messages(tick, cl[c]["client_next"], leader, N)[v]
+                targets.append((name, c, leader))
+                for be in (g, r):
+                    be.write_queue(c, leader, 0, msgs)
+        assert len(targets) == 13 and targets[-1][0] == "two"
+        for name, c, leader in targets:
+            assert g.read_queue(c, leader, 0) == r.read_queue(c, leader, 0), name
+        pairing.same(g, r, "the written queues")
+        before = r.counters()
+        pairing.run(g, r, (1000, 1000, 1000, 37), "launch")
+        cg = pairing.same_counters(g, r)
+        for k in ("client_injected", "redirects", "entries_appended", "ev_rv"):   # the burst ran
+            assert cg[k] > before[k], k
+        for name, c, leader in targets:                               # the written values' fate
+            log = r.log(c, leader)
+            assert g.log(c, leader) == log, name
+            if name == "future":            # appended behind the burst's first client-set
+                assert 9004 in [v for _, v in log[1:]], log[:8]
 
 
 def test_gpu_burst_sharded_handle_equals_single():

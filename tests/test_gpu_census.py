@@ -9,23 +9,11 @@ import pytest
 
 import census_oracle as co
 import helpers
+import pairing
+from cases import CASES, PARITY, cfg_of
 from raftsim import _abi, dist
-from test_gpu_parity import CASES
 
 pytestmark = pytest.mark.gpu
-
-# case, clusters, checkpoints: the runs of test_census_abi.POPULATIONS, one per N = 2..9; where
-# that table lists one tick, half of it first. 333 and 96 are no multiples of floor(64/N) except
-# 96 at N = 8, so "n8" at 333 clusters (333 = 41 * 8 + 5) runs beside the table's N = 8 case.
-PARITY = [("n2", 333, (10000, 20000)), ("n3", 333, (10000, 20000)), ("n4", 333, (10000, 20000)),
-          ("fast_timers", 333, (1000, 2000)), ("n6", 333, (10000, 20000)),
-          ("burst_faults_mid_n7", 96, (2500, 5000)), ("burst_variant_mid_n8", 96, (1250, 2500)),
-          ("n8", 333, (10000, 20000)), ("burst_faults_mid_n9", 96, (2500, 5000))]
-
-
-def cfg_of(name, n, **extra):
-    return dict(CASES[name], n_clusters=n, **extra)
-
 
 def check_identities(c):
     assert sum(c["leaders_hist"]) == sum(c["live_hist"]) == c["clusters"]
@@ -148,8 +136,7 @@ def test_steady_path_is_read_as_it_stands(name, ticks, mode, monkeypatch):
         monkeypatch.setenv("RAFTSIM_STEADY", mode)
     cfg = dict(CASES[name])
     assert 1000 <= cfg["n_clusters"] <= 1200
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
+    r = pairing.oracle(cfg)
     g = helpers.gpu(**cfg)
     for _ in range(ticks // 10000):
         g.step(10000)
@@ -164,9 +151,9 @@ def test_steady_path_is_read_as_it_stands(name, ticks, mode, monkeypatch):
     g.step(10000)
     r.step(10000)
     assert g.diag_last_bails() >= 0
-    assert np.array_equal(g.digest(), r.digest())
+    pairing.same(g, r, "the step after the queries")
     assert g.census() == co.of_backend(r)[0]
-    assert g.counters() == r.counters()
+    pairing.same_counters(g, r)
     g.close()
 
 

@@ -15,21 +15,15 @@ import pytest
 
 import gather_mirror as gm
 import helpers
+import pairing
 import raftsim
+from cases import CASES, GPU_CASES, ROUNDTRIP
 from raftsim import _abi
-from test_gather_abi import GPU_CASES, ROUNDTRIP
-from test_gpu_parity import CASES, _client_set_into
 
 pytestmark = pytest.mark.gpu
 
 SUMS = ["node_ticks"] + _abi.COUNTER_NAMES
 STEADY = dict(n_clusters=1024, nodes=5, hb=300, el_base=500, el_span=500)
-
-
-def oracle_of(cfg):
-    ref = helpers.oracle(**cfg)
-    helpers.oracle_threads(ref, min(helpers.cpu_threads(), 8))
-    return ref
 
 
 def oracle_clone(ref, sources, targets):
@@ -64,7 +58,7 @@ def test_in_handle(name):
     sources = list(range(third)) * 2
     targets = list(range(C - 1, C - 1 - third, -1)) + list(range(third, 2 * third))
     rest = np.setdiff1d(np.arange(C), targets)
-    g, ref = helpers.gpu(**cfg), oracle_of(cfg)
+    g, ref = helpers.gpu(**cfg), pairing.oracle(cfg, threads=8)
     g.step(ticks)
     ref.step(ticks)
     if name == "c4_n9":                                  # more than one workgroup per pair
@@ -91,9 +85,7 @@ def test_in_handle(name):
     oracle_clone(ref, sources, targets)
     assert np.array_equal(now, ref.digest())
     g0, r0 = g.counters(), ref.counters()
-    for h in (g, ref):
-        h.step(4000)
-    assert np.array_equal(g.digest(), ref.digest())
+    pairing.step(g, ref, 4000, "after the clone")
     assert deltas(g.counters(), g0) == deltas(ref.counters(), r0)
     for h in (g, ref):
         h.close()
@@ -132,7 +124,7 @@ def test_owed_draws_and_certificates():
     launches certificates are set and the followers' draws are owed. A clone that resolved a draw
     with the target's id, passed FL_DRAW through or copied the certificate would differ from the
     host path and from the oracle, at once or a step later."""
-    g, twin, ref = helpers.gpu(**STEADY), helpers.gpu(**STEADY), oracle_of(STEADY)
+    g, twin, ref = helpers.gpu(**STEADY), helpers.gpu(**STEADY), pairing.oracle(STEADY, threads=8)
     for _ in range(3):
         for h in (g, twin):
             h.step(10000)
@@ -156,18 +148,16 @@ def test_owed_draws_and_certificates():
 
 def test_cross_handle_a_queued_client_set_ends_lite():
     cfg = dict(n_clusters=64, nodes=5, hb=300, el_base=500, el_span=500)
-    src, ref = helpers.gpu(**cfg), oracle_of(cfg)
+    src, ref = helpers.gpu(**cfg), pairing.oracle(cfg, threads=8)
     for h in (src, ref):
         h.step(3000)
         for c, node in ((2, 1), (40, 3)):
-            _client_set_into(h, c, node, 700 + c)
+            helpers.client_set_into(h, c, node, 700 + c)
     tgt = helpers.gpu(**cfg)                             # a LITE handle until the clone
     tgt.set_tick(3000)
     assert tgt.clone(range(64), range(64), source=src) == 64
     assert np.array_equal(tgt.digest(), src.digest())
-    for h in (tgt, ref):
-        h.step(3000)
-    assert np.array_equal(tgt.digest(), ref.digest())
+    pairing.step(tgt, ref, 3000, "the clone's target")
     assert tgt.counters()["ev_cs"] >= 2                  # the two client-sets were handled
     for h in (src, ref, tgt):
         h.close()

@@ -13,11 +13,11 @@ import pytest
 
 import gather_mirror as gm
 import helpers
+import pairing
 import raftsim
 import viol_oracle
+from cases import CASES, GPU_CASES, ROUNDTRIP
 from raftsim import ClusterPack, _abi
-from test_gather_abi import GPU_CASES, ROUNDTRIP
-from test_gpu_parity import CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -44,10 +44,8 @@ def raw_gather(g, ids, mask, cap=None):
 def test_every_part_equals_the_mirror(name):
     cfg, ticks = GPU_CASES[name]
     C = cfg["n_clusters"]
-    g, ref = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(ref, min(helpers.cpu_threads(), 8))
+    g, ref = helpers.gpu(**cfg), pairing.oracle(cfg, threads=8, ticks=ticks)
     g.step(ticks)
-    ref.step(ticks)
     ids = list(range(C))
     pack = g.gather(ids)
     assert pack.parts == gm.PARTS and pack.tick == ticks and pack.clusters == ids

@@ -8,208 +8,20 @@ import numpy as np
 import pytest
 
 import helpers
+import pairing
+from cases import BURSTS, C4_BURSTS, CASES, FAULTS
+from helpers import client_set_into
 
 pytestmark = pytest.mark.gpu
-
-FAULTS = dict(drop_ppm=100000, dup_ppm=10000, dmin=1, dmax=50, part_ppm=100000)
-# SIM_SPEC D14/D15: bursts of client traffic with quiet gaps longer than the election timeout,
-# and clients that follow redirect-client (server.clj:62-63) to the leader
-BURSTS = dict(client_period=16384, client_burst=2048, client_redirects=4)
-C4_BURSTS = dict(log_cap=4096, client_ppm=500000, client_period=8192, client_burst=2048,
-                 client_redirects=4)
-# the burst-engine fault cases: short timers and delays with drops, partitions and duplicates
-# (medium client rate), and config-4-rate bursts under fast timers
-MID = dict(hb=100, el_base=150, el_span=150, dmin=1, dmax=8, drop_ppm=100000, part_ppm=100000,
-           dup_ppm=10000)
-FAST = dict(hb=300, el_base=500, el_span=500)
-B4 = dict(log_cap=4096, client_ppm=500000, client_period=4096, client_burst=1024,
-          client_redirects=4)
-
-CASES = {
-    # C2 shape (no faults, no client traffic), smaller cluster count
-    "c2_small": dict(n_clusters=4096, nodes=5, seed=42),
-    # C3 shape: faults, partitions, client-set
-    "c3_faults": dict(n_clusters=2048, nodes=5, seed=1, client_ppm=1000, log_cap=256, **FAULTS),
-    # C4 shape: 7 and 9 nodes, client-heavy, long logs
-    "c4_n7": dict(n_clusters=1024, nodes=7, seed=3, client_ppm=3000, log_cap=512,
-                  commit_stream_cap=256),
-    "c4_n9": dict(n_clusters=512, nodes=9, seed=5, client_ppm=2000, log_cap=1024, dup_ppm=20000,
-                  dmax=8),
-    # C5: bug variant (vote granted without the log check)
-    "c5_variant": dict(n_clusters=1024, nodes=5, seed=9, client_ppm=1000, log_cap=256,
-                       variant_flags=1, commit_stream_cap=7, **FAULTS),
-    # overflow and tiny inboxes, heavy duplication
-    "overflow": dict(n_clusters=512, nodes=9, seed=11, inbox_cap=2, dup_ppm=300000, dmax=3,
-                     client_ppm=5000, log_cap=64),
-    # arena pressure: arena == 2L, short logs, frequent client-sets
-    "arena_tight": dict(n_clusters=512, nodes=5, seed=13, client_ppm=20000, log_cap=16,
-                        arena_cap=32, dup_ppm=100000, dmax=10),
-    # arena sizes that are not a multiple of the 8-slot chunks of the arena loops (tick_wave.hpp):
-    # runs wrap inside a chunk, and chunks read past an arena's end into the next one
-    "arena_odd": dict(n_clusters=512, nodes=5, seed=14, client_ppm=20000, log_cap=16,
-                      arena_cap=37, hb=40, el_base=60, el_span=60, dup_ppm=100000, dmax=10,
-                      commit_stream_cap=5),
-    "spec_arena_odd": dict(n_clusters=512, nodes=5, seed=15, client_ppm=30000, log_cap=24,
-                           arena_cap=51, hb=40, el_base=60, el_span=60, variant_flags=2, **FAULTS),
-    # launch boundaries that split ticks oddly
-    "tiny_launches": dict(n_clusters=300, nodes=5, seed=17, client_ppm=1000, ticks_per_launch=7,
-                          **FAULTS),
-    "n2": dict(n_clusters=700, nodes=2, seed=19, client_ppm=500, **FAULTS),
-    "n3": dict(n_clusters=700, nodes=3, seed=21, client_ppm=500, **FAULTS),
-    "n4": dict(n_clusters=700, nodes=4, seed=23, client_ppm=500, **FAULTS),
-    "n6": dict(n_clusters=700, nodes=6, seed=25, client_ppm=500, **FAULTS),
-    "n8": dict(n_clusters=700, nodes=8, seed=27, client_ppm=500, **FAULTS),
-    # F3 trace rings on (they enter the digest): wrap-around, entry-ring overwrite, evictions
-    "traced": dict(n_clusters=1024, nodes=5, seed=31, client_ppm=2000, log_cap=128, trace_cap=48,
-                   trace_entry_cap=300, commit_stream_cap=16, **FAULTS),
-    "traced_tight": dict(n_clusters=256, nodes=9, seed=33, client_ppm=20000, log_cap=16,
-                         arena_cap=32, dup_ppm=100000, dmax=10, trace_cap=16, trace_entry_cap=64),
-    "fast_timers": dict(n_clusters=1000, nodes=5, seed=29, hb=30, el_base=50, el_span=50,
-                        client_ppm=20000, log_cap=128, **FAULTS),
-    # F4 Spec-Raft control (SIM_SPEC §8) and its bug-injected form
-    "spec_c3": dict(n_clusters=2048, nodes=5, seed=41, client_ppm=2000, log_cap=256,
-                    variant_flags=2, commit_stream_cap=64, **FAULTS),
-    "spec_nolog": dict(n_clusters=1024, nodes=5, seed=43, client_ppm=5000, log_cap=512, hb=300,
-                       el_base=500, el_span=500, variant_flags=3, **FAULTS),
-    "spec_n9": dict(n_clusters=512, nodes=9, seed=45, client_ppm=3000, log_cap=1024,
-                    variant_flags=2, commit_stream_cap=256, dup_ppm=20000, dmax=8),
-    "spec_n4_traced": dict(n_clusters=512, nodes=4, seed=47, client_ppm=4000, log_cap=128,
-                           variant_flags=2, trace_cap=32, trace_entry_cap=256, **FAULTS),
-    "spec_tight": dict(n_clusters=512, nodes=3, seed=49, client_ppm=30000, log_cap=24,
-                       arena_cap=48, hb=40, el_base=60, el_span=60, variant_flags=2,
-                       inbox_cap=3, **FAULTS),
-    # BASELINE config 4: 7 and 9 nodes, 4096-entry logs, bursts that build 1000+-entry batches
-    "c4_n7_bursts": dict(n_clusters=512, nodes=7, seed=3, commit_stream_cap=256, **C4_BURSTS),
-    "c4_n9_bursts": dict(n_clusters=256, nodes=9, seed=5, dup_ppm=20000, dmax=8, **C4_BURSTS),
-    # the N >= 7 burst engine's edges (tick_wave.hpp BURST): no redirect hops (abandoned
-    # client-sets) with one-slot inboxes; follower timers and heartbeats that fall inside bursts;
-    # launches that split bursts at odd ticks
-    "burst_edges_n7": dict(n_clusters=512, nodes=7, seed=91, client_ppm=500000, client_period=4096,
-                           client_burst=1024, client_redirects=0, inbox_cap=1, log_cap=700, hb=300,
-                           el_base=500, el_span=500),
-    "burst_timers_n9": dict(n_clusters=512, nodes=9, seed=93, client_ppm=300000, client_period=2048,
-                            client_burst=512, client_redirects=1, inbox_cap=2, log_cap=2000, hb=40,
-                            el_base=60, el_span=40),
-    "burst_launches_n8": dict(n_clusters=512, nodes=8, seed=95, client_ppm=500000,
-                              client_period=1024, client_burst=256, client_redirects=4,
-                              ticks_per_launch=37, log_cap=1500),
-    # the burst engine under faults (tests/test_burst_witness.py shows on the oracle that these
-    # reach its states). Medium client rate, short timers, drops, partitions, duplicates: heartbeats,
-    # fault-caused elections and faulty messages fall between injections, so the engine is entered
-    # after an election and left for a lost heartbeat, with halted nodes and with followers whose
-    # logs are longer than the new leader's (the `pre = own[as]` compare path); n9 fills its logs
-    # (OVERFLOW at log_cap), n8 is the vote-without-log-check variant
-    "burst_faults_mid_n7": dict(n_clusters=256, nodes=7, seed=121, log_cap=1024, client_ppm=30000,
-                                client_redirects=4, **MID),
-    "burst_faults_mid_n9": dict(n_clusters=256, nodes=9, seed=123, log_cap=1024, client_ppm=60000,
-                                client_redirects=2, **MID),
-    "burst_variant_mid_n8": dict(n_clusters=256, nodes=8, seed=125, log_cap=1024, client_ppm=30000,
-                                 client_redirects=4, variant_flags=1, **MID),
-    # ... with an odd arena a little above 2L and no trace rings: the engine's arena wrap and its
-    # read-ahead of the follower's next entry run across the arena's end
-    "burst_arena_odd_n7": dict(n_clusters=256, nodes=7, seed=127, log_cap=48, arena_cap=101,
-                               client_ppm=30000, client_redirects=4, **MID),
-    # C4-rate bursts with faults: messages in flight when a burst starts and when it ends; with
-    # two-slot inboxes on top
-    "burst_faults_c4_n9": dict(n_clusters=256, nodes=9, seed=103, **B4, **FAST, **FAULTS),
-    "burst_faults_n8_inbox2": dict(n_clusters=256, nodes=8, seed=111, inbox_cap=2, **B4, **FAST,
-                                   **FAULTS),
-    # config 3 / 5 shapes with the bursty, redirect-following client
-    "c3_bursts": dict(n_clusters=2048, nodes=5, seed=1, client_ppm=80000, log_cap=256,
-                      **BURSTS, **FAULTS),
-    "spec_bursts": dict(n_clusters=1024, nodes=5, seed=61, client_ppm=80000, log_cap=1024,
-                        variant_flags=2, commit_stream_cap=64, **BURSTS, **FAULTS),
-    "spec_nolog_bursts": dict(n_clusters=1024, nodes=5, seed=63, client_ppm=80000, log_cap=1024,
-                              variant_flags=3, **BURSTS, **FAULTS),
-    # faithful crash storm under client traffic: most client-sets reach halted nodes (to-halted)
-    "crash_storm_clients": dict(n_clusters=2048, nodes=5, seed=13, client_ppm=80000, log_cap=16,
-                                hb=300, el_base=500, el_span=500, **BURSTS, **FAULTS),
-    "redirect_storm": dict(n_clusters=512, nodes=6, seed=65, client_ppm=1000000,
-                           client_period=300, client_burst=40, client_redirects=16, inbox_cap=4,
-                           log_cap=128, hb=50, el_base=80, el_span=80, **FAULTS),
-    # LITE launches (no faults, no client, fixed delay) at N <= 5 take the steady kernel and hand
-    # every other event to the catch-up launch (steady_kernel.hip): its edges
-    "lite_n2": dict(n_clusters=1000, nodes=2, seed=71, hb=40, el_base=60, el_span=40),
-    "lite_n3": dict(n_clusters=1000, nodes=3, seed=73, hb=300, el_base=500, el_span=500),
-    "lite_n4": dict(n_clusters=1000, nodes=4, seed=75, hb=300, el_base=500, el_span=500, dmin=4,
-                    dmax=4),
-    # heartbeats slower than the election timer: elections keep interrupting the rounds
-    "lite_elections": dict(n_clusters=1200, nodes=5, seed=77, hb=700, el_base=500, el_span=400,
-                           dmin=3, dmax=3),
-    # two-slot inboxes: a leader's four responses overflow its RES ring (the slow delivery path)
-    "lite_tiny_inbox": dict(n_clusters=1200, nodes=5, seed=79, inbox_cap=2, hb=200, el_base=500,
-                            el_span=300),
-    # odd launch splits: queued messages cross launch boundaries into the pair cells
-    "lite_odd_launches": dict(n_clusters=600, nodes=5, seed=81, ticks_per_launch=13, hb=60,
-                              el_base=100, el_span=100, dmin=7, dmax=7),
-    # timers too short for the lane kernel's one-trip heartbeat round (hb < 2d + N - 1, el_base <
-    # d + N - 1): every round runs tick by tick, elections keep interrupting them
-    "lite_short_round": dict(n_clusters=1000, nodes=5, seed=85, hb=9, el_base=6, el_span=30,
-                             dmin=3, dmax=3),
-    # LITE launches at N >= 6 have no steady kernel: every launch of a fault-free, client-free
-    # handle runs the general body's LITE instance, tick_kernel<N, 0, 0, LITE> (one copy per
-    # message, the fault-free delivery pack, no PROV / RC / REGS / BURST): a fixed delay above 1;
-    # heartbeats slower than the election timer (NPE halts, messages to halted nodes); four-slot
-    # and one-slot inboxes (a leader's RES ring overflows; with one slot every vote is lost and no
-    # leader is ever elected); 7-tick delays across 13-tick launches; timers shorter than a round
-    "lite_n6": dict(n_clusters=700, nodes=6, seed=171, hb=300, el_base=500, el_span=500),
-    "lite_n7_d4": dict(n_clusters=700, nodes=7, seed=173, hb=300, el_base=500, el_span=500,
-                       dmin=4, dmax=4),
-    "lite_n8_elections": dict(n_clusters=600, nodes=8, seed=175, hb=700, el_base=500, el_span=400,
-                              dmin=3, dmax=3),
-    "lite_n9_inbox4": dict(n_clusters=512, nodes=9, seed=177, inbox_cap=4, hb=200, el_base=500,
-                           el_span=300),
-    "lite_n6_inbox1": dict(n_clusters=512, nodes=6, seed=183, inbox_cap=1, hb=40, el_base=60,
-                           el_span=40, dmin=2, dmax=2),
-    "lite_n9_odd_launches": dict(n_clusters=400, nodes=9, seed=179, ticks_per_launch=13, hb=60,
-                                 el_base=100, el_span=100, dmin=7, dmax=7),
-    "lite_n7_short_round": dict(n_clusters=512, nodes=7, seed=181, hb=9, el_base=6, el_span=30,
-                                dmin=3, dmax=3),
-    # fault-free Spec-Raft handles: DevSim::lite is set (rebuild period 8, first launch unpacked,
-    # no storm split) but the kernel is tick_kernel<N, 0, SPEC, 0>; at N = 6 the one N = 6 instance
-    # with REGS and one wave per SIMD
-    "spec_lite_n5": dict(n_clusters=700, nodes=5, seed=185, hb=300, el_base=500, el_span=500,
-                         variant_flags=2),
-    "spec_lite_n6_elections": dict(n_clusters=512, nodes=6, seed=191, hb=700, el_base=500,
-                                   el_span=400, dmin=3, dmax=3, variant_flags=2),
-    "spec_lite_n9_inbox4": dict(n_clusters=512, nodes=9, seed=193, inbox_cap=4, hb=200,
-                                el_base=500, el_span=300, variant_flags=2),
-    # a fault-free traced faithful handle, tick_kernel<6, TRACE, 0, 0> with DevSim::lite set: the
-    # 16-event trace ring wraps
-    "traced_lite_n6": dict(n_clusters=256, nodes=6, seed=189, hb=40, el_base=60, el_span=40,
-                           dmin=2, dmax=2, trace_cap=16, trace_entry_cap=8),
-}
-
-
-def run_pair(cfg, ticks, chunk):
-    g = helpers.gpu(**cfg)
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    done = 0
-    while done < ticks:
-        n = min(chunk, ticks - done)
-        g.step(n)
-        r.step(n)
-        done += n
-        dg, dr = g.digest(), r.digest()
-        bad = np.nonzero(dg != dr)[0]
-        if len(bad):
-            c = int(bad[0])
-            msg = (f"{len(bad)} of {cfg['n_clusters']} clusters differ after {done} ticks; "
-                   f"first local cluster {c}\n" + helpers.describe_cluster_diff(g, r, c) + "\n"
-                   + helpers.bisect_divergence(cfg, cfg.get("cluster_offset", 0) + c, done,
-                                               helpers.gpu, helpers.oracle))
-            pytest.fail(msg)
-    return g, r
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_gpu_matches_oracle(name):
     cfg = CASES[name]
-    g, r = run_pair(cfg, 20000, 5000)
-    cg, cr = g.counters(), r.counters()
-    assert cg == cr
-    assert cg["node_ticks"] == cfg["n_clusters"] * cfg["nodes"] * 20000
+    with pairing.pair(cfg) as (g, r):
+        pairing.run(g, r, [5000] * 4, bisect=cfg)
+        cg = pairing.same_counters(g, r)
+        assert cg["node_ticks"] == cfg["n_clusters"] * cfg["nodes"] * 20000
 
 
 @pytest.mark.parametrize("seed", [1, 42, 0xDEADBEEF, 0x1_2345_6789])
@@ -221,16 +33,14 @@ def test_gpu_c2_full_size(seed):
     would be handed to the general body); the last one is the steady kernel alone on the
     256-workgroup grid with no cluster bailed (core.clj:91-139,105-123,141-149,162-169,181)."""
     cfg = dict(n_clusters=65536, nodes=5, seed=seed)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
     bails = []
-    for launch in range(4):
-        g.step(10000)
-        r.step(10000)
-        bails.append(g.diag_last_bails())
-        bad = np.nonzero(g.digest() != r.digest())[0]
-        assert not len(bad), f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}"
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg) as (g, r):
+        for launch in range(4):
+            g.step(10000)
+            r.step(10000)
+            bails.append(g.diag_last_bails())
+            pairing.same(g, r, f"launch {launch}")
+        pairing.same_counters(g, r)
     assert 0 <= bails[0] <= 2 and bails[-1] == 0, bails
 
 
@@ -247,28 +57,23 @@ def test_gpu_storm_window(variant, nodes):
     cfg = dict(n_clusters=4096, nodes=nodes, seed=11 + variant, hb=400, el_base=1500, el_span=800,
                client_ppm=300000, client_period=4096, client_burst=1024, client_redirects=4,
                log_cap=256, variant_flags=variant, drop_ppm=50000, dmin=1, dmax=20)
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    g = helpers.gpu(ticks_per_launch=4000, **cfg)
-    g.step(4000)
-    r.step(4000)
-    assert g.last_step_timing()[1] == 2                  # [0, 1500) storm, then [1500, 4000)
-    assert np.array_equal(g.digest(), r.digest())
-    g.step(4000)
-    r.step(4000)
-    assert g.last_step_timing()[1] == 1
-    assert np.array_equal(g.digest(), r.digest())
-    c = g.counters()
-    assert c == r.counters() and c["redirects"] > 0 and c["leaders"] > 0
-    g.close()
-    g2 = helpers.gpu(ticks_per_launch=4000, **cfg)
-    g2.set_tick(0)                                       # a host write of the clock
-    g2.step(4000)
-    assert g2.last_step_timing()[1] == 1
-    r2 = helpers.oracle(**cfg)
-    helpers.oracle_threads(r2, helpers.cpu_threads())
-    r2.step(4000)
-    assert np.array_equal(g2.digest(), r2.digest())
+    with pairing.pair(cfg, dict(ticks_per_launch=4000)) as (g, r):
+        g.step(4000)
+        r.step(4000)
+        assert g.last_step_timing()[1] == 2              # [0, 1500) storm, then [1500, 4000)
+        pairing.same(g, r, "storm step")
+        g.step(4000)
+        r.step(4000)
+        assert g.last_step_timing()[1] == 1
+        pairing.same(g, r, "second step")
+        c = pairing.same_counters(g, r)
+        assert c["redirects"] > 0 and c["leaders"] > 0
+    with pairing.pair(cfg, dict(ticks_per_launch=4000)) as (g2, r2):
+        g2.set_tick(0)                                   # a host write of the clock
+        g2.step(4000)
+        assert g2.last_step_timing()[1] == 1
+        r2.step(4000)
+        pairing.same(g2, r2, "step after set_tick(0)")
 
 
 @pytest.mark.parametrize("variant,inbox,nodes", [(0, 16, 5), (2, 2, 5), (0, 16, 3), (2, 16, 9),
@@ -284,17 +89,15 @@ def test_gpu_storm_engine(variant, inbox, nodes):
                el_span=2000, client_ppm=200000, client_period=8192, client_burst=2048,
                client_redirects=4, inbox_cap=inbox, log_cap=128, variant_flags=variant,
                drop_ppm=100000, dmin=1, dmax=30, part_ppm=50000)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
     bails = []
-    for _ in range(4):
-        g.step(1250)
-        r.step(1250)
-        if g.tick <= 3000 + 1250:
-            bails.append(g.diag_storm_bails())
-        bad = np.nonzero(g.digest() != r.digest())[0]
-        assert not len(bad), f"tick {g.tick}: {len(bad)} clusters differ, first {bad[0]}"
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg) as (g, r):
+        for _ in range(4):
+            g.step(1250)
+            r.step(1250)
+            if g.tick <= 3000 + 1250:
+                bails.append(g.diag_storm_bails())
+            pairing.same(g, r, "launch")
+        pairing.same_counters(g, r)
     assert bails and min(bails) >= 0, bails              # the storm kernel ran every storm launch
     if inbox >= 16:
         assert max(bails) < 131072 // 4, bails
@@ -309,24 +112,15 @@ def test_gpu_init_election_closed_form(nodes, d):
     each launch, with few clusters bailed (core.clj:91-139,166-169)."""
     cfg = dict(n_clusters=16384, nodes=nodes, seed=7 + nodes, hb=300, el_base=700, el_span=900,
                dmin=d, dmax=d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
     bails = []
-    for launch in range(3):
-        g.step(3000)
-        r.step(3000)
-        bails.append(g.diag_last_bails())
-        bad = np.nonzero(g.digest() != r.digest())[0]
-        assert not len(bad), f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}"
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg) as (g, r):
+        for launch in range(3):
+            g.step(3000)
+            r.step(3000)
+            bails.append(g.diag_last_bails())
+            pairing.same(g, r, f"launch {launch}")
+        pairing.same_counters(g, r)
     assert 0 <= bails[0] < 16384 // 20, bails
-
-
-def _client_set_into(be, cluster, node, value):
-    """Append a client-set (SIM_SPEC §3, server.clj:12) to a node's REQ queue, arriving now."""
-    q = [list(m) for m in be.read_queue(cluster, node, 0)]
-    arr = max([be.tick] + [m[0] for m in q])
-    be.write_queue(cluster, node, 0, q + [[arr, 3, 0, value, 0, 0, 0, 0]])
 
 
 @pytest.mark.parametrize("mode", ["auto", "always", "never"])
@@ -344,39 +138,34 @@ def test_gpu_host_writes_after_lite_launches(event, mode, monkeypatch):
     monkeypatch.setenv("RAFTSIM_STEADY", mode)
     cfg = dict(n_clusters=4096, nodes=5, seed=42, ticks_per_launch=1000, log_cap=64)
     for phase in (0, 3):
-        g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-        helpers.oracle_threads(r, helpers.cpu_threads())
-        for _ in range(14 + phase):
-            g.step(1000)
-            r.step(1000)
-        for be in (g, r):
-            if event == "set_tick":
-                be.set_tick(be.tick + 777)
-            elif event == "client_set":
-                for c in (5, 100, 4095):
-                    _client_set_into(be, c, 1 + c % 5, 1000 + c)
-            elif event == "client_cursor":
-                be.write_clusters(7, [dict(hwm=(0, 0, 0), client_next=be.tick + 100,
-                                           client_count=0)])
-            else:
-                for c in (3, 200, 4000):
-                    raw = be.read_nodes_raw(c, 1)
-                    lead = next(i for i in range(5) if raw[i].role == 2)
-                    if event == "node_term":           # a follower one term ahead
-                        raw[(lead + 1) % 5].current_term += 1
-                    else:                              # the leader's log gets a committed entry
-                        be.write_arena(c, lead + 1, [(raw[lead].current_term, 77)])
-                        raw[lead].log_len = 1
-                        raw[lead].commit_index = 1
-                        raw[lead].arena_base = 0
-                        raw[lead].arena_frontier = 1
-                    be.write_nodes(c, raw)
-        for launch in range(10):
-            g.step(1000)
-            r.step(1000)
-            bad = np.nonzero(g.digest() != r.digest())[0]
-            assert not len(bad), f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}"
-        assert g.counters() == r.counters()
+        with pairing.pair(cfg) as (g, r):
+            for _ in range(14 + phase):
+                g.step(1000)
+                r.step(1000)
+            for be in (g, r):
+                if event == "set_tick":
+                    be.set_tick(be.tick + 777)
+                elif event == "client_set":
+                    for c in (5, 100, 4095):
+                        client_set_into(be, c, 1 + c % 5, 1000 + c)
+                elif event == "client_cursor":
+                    be.write_clusters(7, [dict(hwm=(0, 0, 0), client_next=be.tick + 100,
+                                               client_count=0)])
+                else:
+                    for c in (3, 200, 4000):
+                        raw = be.read_nodes_raw(c, 1)
+                        lead = next(i for i in range(5) if raw[i].role == 2)
+                        if event == "node_term":           # a follower one term ahead
+                            raw[(lead + 1) % 5].current_term += 1
+                        else:                              # the leader's log gets a committed entry
+                            be.write_arena(c, lead + 1, [(raw[lead].current_term, 77)])
+                            raw[lead].log_len = 1
+                            raw[lead].commit_index = 1
+                            raw[lead].arena_base = 0
+                            raw[lead].arena_frontier = 1
+                        be.write_nodes(c, raw)
+            pairing.run(g, r, [1000] * 10, "launch")
+            pairing.same_counters(g, r)
 
 
 @pytest.mark.parametrize("nodes,variant_flags,steady_mode,moved", [
@@ -418,63 +207,54 @@ def test_gpu_host_written_logs_wrap_odd_arena(nodes, variant_flags, steady_mode,
                variant_flags=variant_flags)
     if nodes == 9:
         cfg.update(dmin=3, dmax=3)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    g.step(1500)
-    r.step(1500)
-    assert np.array_equal(g.digest(), r.digest())
-    before = r.counters()
-    recs = r.read_nodes()
-    written = clean = 0
-    for c in range(cfg["n_clusters"]):
-        leads = [i for i in range(nodes)
-                 if recs[c * nodes + i]["role"] == 2 and recs[c * nodes + i]["fault"] == 0]
-        if len(leads) != 1:
-            continue
-        lead = leads[0]
-        written += 1
-        clean += c % 2 == 0
-        base = A - 1 - c % 5
-        for be in (g, r):
-            raw = be.read_nodes_raw(c, 1)
-            term = raw[lead].current_term
-            arena = [(0, 0)] * A
-            for j in range(k):
-                arena[(base + j) % A] = (term if j >= k // 2 else max(1, term - 1), 1000 * c + j)
-            be.write_arena(c, lead + 1, arena)
-            raw[lead].log_len = k
-            raw[lead].commit_index = (c % 3) * (k // 2)
-            raw[lead].arena_base = base
-            raw[lead].arena_frontier = base + k
-            for i in range(nodes if moved else 0):
-                if i == lead or raw[i].log_len:
-                    continue
-                fb = A - 2 - (c + i) % 3
-                raw[i].arena_base = raw[i].arena_frontier = fb
-                if c % 2 == 0:
-                    be.write_arena(c, i + 1, [(0, 0)] * fb + [arena[base % A]])
-                    raw[i].log_len = 1
-                    raw[i].arena_frontier = fb + 1
-            be.write_nodes(c, raw)
-    assert np.array_equal(g.digest(), r.digest()), "state load differs"
-    for launch in range(6):
-        g.step(500)
-        r.step(500)
-        bad = np.nonzero(g.digest() != r.digest())[0]
-        assert not len(bad), (f"launch {launch}: {len(bad)} clusters differ, first {bad[0]}\n"
-                              + helpers.describe_cluster_diff(g, r, int(bad[0])))
-    cg, cr = g.counters(), r.counters()
-    assert cg == cr
-    # witnesses, on the oracle's counters: the written logs were shipped whole and, in the
-    # faithful model, re-appended until logs overflowed
-    assert written >= 150
-    assert cr["entries_appended"] - before["entries_appended"] >= 150 * (nodes - 1) * (k - 1)
-    if variant_flags == 0:
-        assert cr["halt_overflow"] > 0 and cr["viol_log"] > 0
-    if moved and variant_flags == 0:     # one violation per follower, in the odd clusters alone
-        assert clean >= 75 and cr["viol_log"] == (written - clean) * (nodes - 1)
-    if steady_mode is not None:
-        assert (g.diag_last_bails() >= 0) == (steady_mode == "always")
+    with pairing.pair(cfg) as (g, r):
+        pairing.step(g, r, 1500)
+        before = r.counters()
+        recs = r.read_nodes()
+        written = clean = 0
+        for c in range(cfg["n_clusters"]):
+            leads = [i for i in range(nodes)
+                     if recs[c * nodes + i]["role"] == 2 and recs[c * nodes + i]["fault"] == 0]
+            if len(leads) != 1:
+                continue
+            lead = leads[0]
+            written += 1
+            clean += c % 2 == 0
+            base = A - 1 - c % 5
+            for be in (g, r):
+                raw = be.read_nodes_raw(c, 1)
+                term = raw[lead].current_term
+                arena = [(0, 0)] * A
+                for j in range(k):
+                    arena[(base + j) % A] = (term if j >= k // 2 else max(1, term - 1), 1000 * c + j)
+                be.write_arena(c, lead + 1, arena)
+                raw[lead].log_len = k
+                raw[lead].commit_index = (c % 3) * (k // 2)
+                raw[lead].arena_base = base
+                raw[lead].arena_frontier = base + k
+                for i in range(nodes if moved else 0):
+                    if i == lead or raw[i].log_len:
+                        continue
+                    fb = A - 2 - (c + i) % 3
+                    raw[i].arena_base = raw[i].arena_frontier = fb
+                    if c % 2 == 0:
+                        be.write_arena(c, i + 1, [(0, 0)] * fb + [arena[base % A]])
+                        raw[i].log_len = 1
+                        raw[i].arena_frontier = fb + 1
+                be.write_nodes(c, raw)
+        pairing.same(g, r, "state load")
+        pairing.run(g, r, [500] * 6, "launch")
+        cr = pairing.same_counters(g, r)
+        # witnesses, on the oracle's counters: the written logs were shipped whole and, in the
+        # faithful model, re-appended until logs overflowed
+        assert written >= 150
+        assert cr["entries_appended"] - before["entries_appended"] >= 150 * (nodes - 1) * (k - 1)
+        if variant_flags == 0:
+            assert cr["halt_overflow"] > 0 and cr["viol_log"] > 0
+        if moved and variant_flags == 0:     # one violation per follower, in the odd clusters alone
+            assert clean >= 75 and cr["viol_log"] == (written - clean) * (nodes - 1)
+        if steady_mode is not None:
+            assert (g.diag_last_bails() >= 0) == (steady_mode == "always")
 
 
 @pytest.mark.parametrize("nodes", [7, 9])
@@ -483,11 +263,11 @@ def test_gpu_c4_logs_reach_capacity(nodes):
     carry 1000+ entries (core.clj:56-67 ships the whole suffix), and OVERFLOW halts appear (D8);
     GPU == oracle on every cluster, counter and the payload maximum."""
     cfg = dict(n_clusters=64, nodes=nodes, seed=7 + nodes, **C4_BURSTS)
-    g, r = run_pair(cfg, 110000, 55000)
-    cg, cr = g.counters(), r.counters()
-    assert cg == cr
-    assert cg["payload_max"] >= 1000 and cg["halt_overflow"] > 0
-    assert max(n["log_len"] for n in g.read_nodes()) >= 3000
+    with pairing.pair(cfg) as (g, r):
+        pairing.run(g, r, [55000] * 2, bisect=cfg)
+        cg = pairing.same_counters(g, r)
+        assert cg["payload_max"] >= 1000 and cg["halt_overflow"] > 0
+        assert max(n["log_len"] for n in g.read_nodes()) >= 3000
 
 
 def test_gpu_sharded_handle_equals_single():
@@ -539,8 +319,7 @@ def test_gpu_spec_raft_safety_at_scale():
     assert b["viol_complete"] > 0 and b["first_violation_tick"] is not None
     lo = 4096
     for flags, sim in ((2, ctl), (3, bug)):
-        r = helpers.oracle(**dict(base, n_clusters=lo, variant_flags=flags))
-        helpers.oracle_threads(r, helpers.cpu_threads())
+        r = pairing.oracle(dict(base, n_clusters=lo, variant_flags=flags))
         r.step(20000)
         assert np.array_equal(sim.digest(0, lo), r.digest())
 
@@ -592,11 +371,9 @@ def test_gpu_multi_launch_step():
     """One raft_sim_step spanning several launches (ticks_per_launch < n_ticks) equals the oracle."""
     cfg = dict(n_clusters=512, nodes=5, seed=81, client_ppm=20000, log_cap=64,
                ticks_per_launch=3000, **BURSTS, **FAULTS)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    g.step(17000)
-    r.step(17000)
-    assert g.tick == r.tick == 17000
-    assert np.array_equal(g.digest(), r.digest()) and g.counters() == r.counters()
+    with pairing.pair(cfg, threads=1) as (g, r):
+        pairing.step(g, r, 17000, counters=True)
+        assert g.tick == 17000
 
 
 def test_gpu_tick_horizon():
@@ -656,18 +433,12 @@ def test_gpu_host_written_client_cursor(ppm):
     honoured like any other, also with client_ppm = 0, where every power of the gap search is
     2^32 and the next injection never comes (SIM_SPEC §4 P0)."""
     cfg = dict(n_clusters=64, nodes=5, seed=77, client_ppm=ppm, log_cap=64)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
     recs = [dict(hwm=(0, 0, 0), client_next=100 + 37 * i, client_count=i) for i in range(64)]
-    g.write_clusters(0, recs)
-    r.write_clusters(0, recs)
-    for _ in range(3):
-        g.step(4000)
-        r.step(4000)
-        assert (g.digest() == r.digest()).all()
-    assert g.counters() == r.counters()
-    assert g.counters()["client_injected"] >= 64
-
-
+    with pairing.pair(cfg, threads=1) as (g, r):
+        g.write_clusters(0, recs)
+        r.write_clusters(0, recs)
+        pairing.run(g, r, [4000] * 3)
+        assert pairing.same_counters(g, r)["client_injected"] >= 64
 
 
 def test_gpu_steady_path_taken():
@@ -676,16 +447,14 @@ def test_gpu_steady_path_taken():
     leader the steady kernel runs every cluster alone (0 bails); the state equals the oracle's
     after every launch."""
     cfg = dict(n_clusters=8192, nodes=5, seed=83)
-    g = helpers.gpu(**cfg)
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
     bails = []
-    for _ in range(4):
-        g.step(10000)
-        r.step(10000)
-        bails.append(g.diag_last_bails())
-        assert (g.digest() == r.digest()).all()
-    assert g.counters() == r.counters()
+    with pairing.pair(cfg) as (g, r):
+        for launch in range(4):
+            g.step(10000)
+            r.step(10000)
+            bails.append(g.diag_last_bails())
+            pairing.same(g, r, f"launch {launch}")
+        pairing.same_counters(g, r)
     assert 0 <= bails[0] <= 2 and bails[-1] == 0, bails
 
 
@@ -701,9 +470,10 @@ def test_gpu_forced_steady_matches_oracle(name, monkeypatch):
     every chunk."""
     monkeypatch.setenv("RAFTSIM_STEADY", "always")
     cfg = CASES[name]
-    g, r = run_pair(cfg, 20000, 5000)
-    assert g.counters() == r.counters()
-    assert g.diag_last_bails() >= 0          # the last launch took the steady path
+    with pairing.pair(cfg) as (g, r):
+        pairing.run(g, r, [5000] * 4, bisect=cfg)
+        pairing.same_counters(g, r)
+        assert g.diag_last_bails() >= 0      # the last launch took the steady path
 
 
 @pytest.mark.parametrize("name", LITE_CASES)
@@ -714,8 +484,9 @@ def test_gpu_forced_general_matches_oracle(name, monkeypatch):
     every chunk."""
     monkeypatch.setenv("RAFTSIM_STEADY", "never")
     cfg = CASES[name]
-    g, r = run_pair(cfg, 20000, 5000)
-    assert g.counters() == r.counters()
-    bails = g.diag_last_bails()
+    with pairing.pair(cfg) as (g, r):
+        pairing.run(g, r, [5000] * 4, bisect=cfg)
+        pairing.same_counters(g, r)
+        bails = g.diag_last_bails()
     print(f"{name}: diag_last_bails {bails}")
     assert bails == -1                       # the last launch did not take the steady path

@@ -15,21 +15,15 @@ import pytest
 
 import gather_mirror as gm
 import helpers
+import pairing
 import raftsim
+from cases import CASES, GPU_CASES, ROUNDTRIP
 from raftsim import ClusterPack, _abi
-from test_gather_abi import GPU_CASES, ROUNDTRIP
-from test_gpu_parity import CASES, _client_set_into
 
 pytestmark = pytest.mark.gpu
 
 ALL = _abi.GATHER_ALL
 SUMS = ["node_ticks"] + _abi.COUNTER_NAMES
-
-
-def oracle_of(cfg):
-    ref = helpers.oracle(**cfg)
-    helpers.oracle_threads(ref, min(helpers.cpu_threads(), 8))
-    return ref
 
 
 def raw_scatter(g, clusters, records, pack, n_records=None, data=None):
@@ -49,7 +43,7 @@ def test_round_trip(name):
     cfg, ticks = GPU_CASES[name]
     C = cfg["n_clusters"]
     ids = list(range(C))
-    src, ref = helpers.gpu(**cfg), oracle_of(cfg)
+    src, ref = helpers.gpu(**cfg), pairing.oracle(cfg, threads=8)
     src.step(ticks)
     pack = src.gather(ids)
     if name == "c4_n9":                                  # more than one workgroup per pair
@@ -215,17 +209,15 @@ def test_steady_path_is_earned_again():
 
 def test_a_queued_client_set_ends_lite():
     cfg = dict(n_clusters=64, nodes=5, hb=300, el_base=500, el_span=500)
-    src, ref = helpers.gpu(**cfg), oracle_of(cfg)
+    src, ref = helpers.gpu(**cfg), pairing.oracle(cfg, threads=8)
     for h in (src, ref):
         h.step(3000)
         for c, node in ((2, 1), (40, 3)):
-            _client_set_into(h, c, node, 700 + c)
+            helpers.client_set_into(h, c, node, 700 + c)
     tgt = helpers.gpu(**cfg)                             # a LITE handle until the scatter
     tgt.set_tick(3000)
     assert tgt.scatter(src.gather(range(64))) == 64
-    for h in (tgt, ref):
-        h.step(3000)
-    assert np.array_equal(tgt.digest(), ref.digest())
+    pairing.step(tgt, ref, 3000, "the scatter's target")
     assert tgt.counters()["ev_cs"] >= 2                  # the two client-sets were handled
     for h in (src, ref, tgt):
         h.close()

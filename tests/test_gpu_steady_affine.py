@@ -5,16 +5,13 @@ GPU is compared with the C oracle: digests, counters and every node record."""
 import pytest
 
 import helpers
-from test_gpu_steady_line0 import both, cut_cfg, elected, same
+import pairing
+from cases import cut_cfg
+from steady_pair import elected, launch, same, step
 
 pytestmark = pytest.mark.gpu
 
 ONE_LAUNCH = 65536       # the most ticks a launch fuses: every step below is one launch
-
-
-def launch(g, r, nt, what):
-    both(g, r, nt, what)
-    assert g.diag_last_bails() >= 0, f"{what}: the steady kernel did not run"
 
 
 @pytest.mark.parametrize("d", [1, 3])
@@ -23,11 +20,11 @@ def test_k_sweep(nodes, d):
     """Launches of P - 1 ticks (K = 0 for every cluster), 2P (K = 1 or 2), 3P + 1 (the lanes of a
     wave on both counts of the band), 17P + 5 and 1000P + 3 (the doubling's longer chains)."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for nt in (P - 1, 2 * P, 3 * P + 1, 17 * P + 5, 1000 * P + 3):
-        assert nt <= ONE_LAUNCH
-        launch(g, r, nt, f"launch of {nt}")
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        elected(g, r, P)
+        for nt in (P - 1, 2 * P, 3 * P + 1, 17 * P + 5, 1000 * P + 3):
+            assert nt <= ONE_LAUNCH
+            launch(g, r, nt, f"launch of {nt}")
 
 
 @pytest.mark.parametrize("nodes,d", [(5, 2), (3, 1)])
@@ -40,17 +37,17 @@ def test_outside_the_band(nodes, d, monkeypatch):
     launch here does run the steady kernel, whatever it bailed before."""
     monkeypatch.setenv("RAFTSIM_STEADY", "always")
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    elected(g, r, P)
-    launch(g, r, 2 * P + 3, "on the schedule")
-    for be in (g, r):
-        be.set_tick(be.tick - 5 * P)
-    launch(g, r, 2 * P, "2P after the clock went back")
-    launch(g, r, 9 * P + 1, "9P + 1 after the clock went back")
-    for be in (g, r):
-        be.set_tick(be.tick + 5)
-    launch(g, r, 3 * P, "3P after the clock went forward")
-    launch(g, r, 4 * P + 1, "after")
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        elected(g, r, P)
+        launch(g, r, 2 * P + 3, "on the schedule")
+        for be in (g, r):
+            be.set_tick(be.tick - 5 * P)
+        launch(g, r, 2 * P, "2P after the clock went back")
+        launch(g, r, 9 * P + 1, "9P + 1 after the clock went back")
+        for be in (g, r):
+            be.set_tick(be.tick + 5)
+        launch(g, r, 3 * P, "3P after the clock went forward")
+        launch(g, r, 4 * P + 1, "after")
 
 
 def test_near_the_horizon():
@@ -62,15 +59,15 @@ def test_near_the_horizon():
     total = 300 * P + 6 + (P + 1) + 40 * P             # elected(), then the two launches
     top = 2 ** 32 - 1 - longest - 1                    # the last tick a step may end at
     start = top - 150 - total
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    for be in (g, r):
-        be.set_tick(start)
-    elected(g, r, P)
-    launch(g, r, P + 1, "P + 1")
-    launch(g, r, 40 * P, "40P")
-    assert g.tick == r.tick == top - 150
-    with pytest.raises(helpers.RaftSimError):
-        g.step(152)
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        for be in (g, r):
+            be.set_tick(start)
+        elected(g, r, P)
+        launch(g, r, P + 1, "P + 1")
+        launch(g, r, 40 * P, "40P")
+        assert g.tick == r.tick == top - 150
+        with pytest.raises(helpers.RaftSimError):
+            g.step(152)
 
 
 def test_default_timers():
@@ -83,11 +80,11 @@ def test_default_timers():
     r = helpers.oracle(**cfg)
     helpers.oracle_idle_skip(r, True)
     for i in range(4):
-        both(a, r, 10000, f"step {i} of 10000")
+        step(a, r, 10000, f"step {i} of 10000")
         assert a.diag_last_bails() >= 0
         b.step(10000)
         same(b, r, f"step {i} in launches of 3500")
-    both(a, r, 65536, "one launch of 65536")
+    step(a, r, 65536, "one launch of 65536")
     assert a.diag_last_bails() >= 0
     b.step(10000)
     r2 = helpers.oracle(**cfg)

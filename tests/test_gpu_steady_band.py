@@ -6,18 +6,14 @@ every node record. tests/test_steady_band_witness.py shows on the oracle alone t
 the clusters they are for (steady_band.py has the plans both files run)."""
 import pytest
 
-import helpers
+import pairing
 import steady_band as sb
-from test_gpu_steady_line0 import both, cut_cfg, elected, same
+from cases import cut_cfg
+from steady_pair import elected, launch, same
 
 pytestmark = pytest.mark.gpu
 
 ONE_LAUNCH = 65536       # the most ticks a launch fuses: every step below is one launch
-
-
-def launch(g, r, nt, what):
-    both(g, r, nt, what)
-    assert g.diag_last_bails() >= 0, f"{what}: the steady kernel did not run"
 
 
 @pytest.mark.parametrize("d", [1, 3])
@@ -27,10 +23,10 @@ def test_both_sides_of_rho(nodes, d):
     and 5P + last + 1 ticks: K1 = 0, then rho = 0, 1, P - 2 and P - 1, with clusters at
     delta <= rho (K1 rounds) and delta > rho (K1 - 1) in the same waves."""
     cfg, P = sb.band_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for nt in sb.rho_launches(nodes, d, P):
-        launch(g, r, nt, f"launch of {nt}")
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        elected(g, r, P)
+        for nt in sb.rho_launches(nodes, d, P):
+            launch(g, r, nt, f"launch of {nt}")
 
 
 @pytest.mark.parametrize("nodes,d", [(5, 2), (3, 1)])
@@ -42,18 +38,18 @@ def test_first_value_outside_the_band(nodes, d, monkeypatch):
     moved clock bails clusters by design, and every launch here is to run the steady kernel."""
     monkeypatch.setenv("RAFTSIM_STEADY", "always")
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for be in (g, r):
-        be.set_tick(be.tick - 1)
-    launch(g, r, 2 * P + 1, "2P + 1 after the clock went back by 1")
-    for be in (g, r):
-        be.set_tick(be.tick - (P - 1))
-    launch(g, r, P, "P after the clock went back by P - 1")
-    launch(g, r, 3 * P + 1, "3P + 1 after the clock went back by P - 1")
-    for be in (g, r):
-        be.set_tick(be.tick + 1)
-    launch(g, r, 2 * P, "2P after the clock went forward by 1")
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        elected(g, r, P)
+        for be in (g, r):
+            be.set_tick(be.tick - 1)
+        launch(g, r, 2 * P + 1, "2P + 1 after the clock went back by 1")
+        for be in (g, r):
+            be.set_tick(be.tick - (P - 1))
+        launch(g, r, P, "P after the clock went back by P - 1")
+        launch(g, r, 3 * P + 1, "3P + 1 after the clock went back by P - 1")
+        for be in (g, r):
+            be.set_tick(be.tick + 1)
+        launch(g, r, 2 * P, "2P after the clock went forward by 1")
 
 
 @pytest.mark.parametrize("clusters", [64, 65, 129])
@@ -64,10 +60,10 @@ def test_full_partial_and_mixed_waves(clusters):
     an event (no store, the predicated stores, the unpredicated ones); the partial wave takes the
     predicated stores throughout. Then 3P + 1 ticks: every cluster of every wave is dirty."""
     cfg, P = cut_cfg(5, 1, clusters)
-    g, r = helpers.gpu(**cfg, ticks_per_launch=ONE_LAUNCH), helpers.oracle(**cfg)
-    elected(g, r, P)
-    sb.align_full_waves((g, r), P, 1)
-    same(g, r, "aligned")
-    for i in range(2 * P):
-        launch(g, r, 1, f"single tick {i}")
-    launch(g, r, 3 * P + 1, "launch of 3P + 1")
+    with pairing.pair(cfg, dict(ticks_per_launch=ONE_LAUNCH), threads=1) as (g, r):
+        elected(g, r, P)
+        sb.align_full_waves((g, r), P, 1)
+        same(g, r, "aligned")
+        for i in range(2 * P):
+            launch(g, r, 1, f"single tick {i}")
+        launch(g, r, 3 * P + 1, "launch of 3P + 1")

@@ -1,23 +1,18 @@
 """The steady kernel (steady_kernel.hip) on the exact thresholds of its fast paths: the configs
 of steady_edges.edge_cfg put every inequality of the certified paths' and the closed-form init
 election's guards at equality, or one below it. Everything here compares the GPU with the C
-oracle after every launch (test_gpu_steady_line0.same: digests, counters and the raw node
+oracle after every launch (steady_pair.same: digests, counters and the raw node
 records of every cluster). test_steady_edge_witness.py shows on the oracle alone that these runs
 contain the ties the thresholds are about. Fault-free, client-free configs of 199 clusters."""
 import pytest
 
-import helpers
+import pairing
 import steady_edges as se
-from test_gpu_steady_line0 import both, same
+from steady_pair import launch
 
 pytestmark = pytest.mark.gpu
 
 TPL = 16384         # ticks_per_launch: every step below is one launch (the longest is 300P)
-
-
-def pair(cfg):
-    cfg = dict(cfg, ticks_per_launch=TPL)
-    return helpers.gpu(**cfg), helpers.oracle(**cfg)
 
 
 def set_mode(monkeypatch, mode):
@@ -25,12 +20,6 @@ def set_mode(monkeypatch, mode):
         monkeypatch.delenv("RAFTSIM_STEADY", raising=False)
     else:
         monkeypatch.setenv("RAFTSIM_STEADY", mode)
-
-
-def launch(g, r, n, what, mode):
-    both(g, r, n, what)
-    if mode == "always":
-        assert g.diag_last_bails() >= 0, f"{what}: the steady kernel did not run"
 
 
 SCHEDULE = [(n, d, "corner", m) for n in (2, 3, 4, 5) for d in (1, 2, 3) for m in ("always", "never")]
@@ -56,21 +45,20 @@ def test_threshold_schedule(nodes, d, variant, mode, monkeypatch):
     settled cluster bails for a threshold."""
     set_mode(monkeypatch, mode)
     cfg, P = se.edge_cfg(nodes, d, variant)
-    g, r = pair(cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    launch(g, r, 300 * P, "election launch", mode)
-    for i in range(2 * P + 2):
-        launch(g, r, 1, f"single tick {i}", mode)
-    unsettled = 0
-    for nt in (P - 1, P, P + 1, 2 * P - 1, 7 * P + 3, 200 * P + 1):
-        unsettled = se.settled(r)[0]
-        launch(g, r, nt, f"launch of {nt}", mode)
-    if variant == "corner" and mode is not None:
-        bails = g.diag_last_bails()
-        print(f"N={nodes} d={d} corner {mode}: last launch bails {bails}, oracle unsettled "
-              f"{unsettled} before it, {se.settled(r)[0]} after, deposed leaders with "
-              f"leader-state in {se.deposed(r)} settled clusters")
-        assert bails <= unsettled + se.C_EDGE // 16
+    with pairing.pair(cfg, dict(ticks_per_launch=TPL)) as (g, r):
+        launch(g, r, 300 * P, "election launch", mode)
+        for i in range(2 * P + 2):
+            launch(g, r, 1, f"single tick {i}", mode)
+        unsettled = 0
+        for nt in (P - 1, P, P + 1, 2 * P - 1, 7 * P + 3, 200 * P + 1):
+            unsettled = se.settled(r)[0]
+            launch(g, r, nt, f"launch of {nt}", mode)
+        if variant == "corner" and mode is not None:
+            bails = g.diag_last_bails()
+            print(f"N={nodes} d={d} corner {mode}: last launch bails {bails}, oracle unsettled "
+                  f"{unsettled} before it, {se.settled(r)[0]} after, deposed leaders with "
+                  f"leader-state in {se.deposed(r)} settled clusters")
+            assert bails <= unsettled + se.C_EDGE // 16
 
 
 @pytest.mark.parametrize("nodes,d", [(5, 1), (4, 2), (2, 3)])
@@ -86,17 +74,15 @@ def test_host_written_ties(nodes, d, monkeypatch):
     for name, write in se.WRITES.items():
         for nt in (1, P + 1):
             what = f"{name}, launch of {nt}"
-            g, r = pair(cfg)
-            launch(g, r, 300 * P, f"{what}: election launch", "always")
-            for i in range(6):
-                launch(g, r, 1, f"{what}: settle {i}", "always")
-            for c in se.WRITTEN:
-                assert write(g, c) == write(r, c), (what, c)
-            launch(g, r, nt, what, "always")
-            for i in range(3 * P):
-                launch(g, r, 1, f"{what}: tick {i} after", "always")
-            g.close()
-            r.close()
+            with pairing.pair(cfg, dict(ticks_per_launch=TPL), threads=1) as (g, r):
+                launch(g, r, 300 * P, f"{what}: election launch", "always")
+                for i in range(6):
+                    launch(g, r, 1, f"{what}: settle {i}", "always")
+                for c in se.WRITTEN:
+                    assert write(g, c) == write(r, c), (what, c)
+                launch(g, r, nt, what, "always")
+                for i in range(3 * P):
+                    launch(g, r, 1, f"{what}: tick {i} after", "always")
 
 
 REWRITTEN = (0, 64, 128, 192)      # the first cluster of each wave of the 199
@@ -117,19 +103,20 @@ def test_general_path_round_in_progress(nodes, monkeypatch):
     threshold of this branch would still compare equal."""
     set_mode(monkeypatch, "always")
     cfg, P = se.edge_cfg(nodes, 1, "corner")
-    g, r = pair(cfg)
-    launch(g, r, 300 * P, "election launch", "always")
-    launch(g, r, 2 * P, f"launch of {2 * P}", "always")
-    for i, nt in enumerate([1] * (2 * P + 2) + [P - 1, P + 1, 3 * P + 1]):
-        unsettled = se.settled(r)[0]
-        for c in REWRITTEN:
-            se.leader_of(r, c)                   # settled: at the fixed point, in some phase
-            for be in (g, r):
-                be.write_nodes(c, be.read_nodes_raw(c, 1))
-        launch(g, r, nt, f"launch {i} of {nt}", "always")
-        bails = g.diag_last_bails()
-        print(f"N={nodes} launch {i} of {nt}: bails {bails}, oracle unsettled {unsettled} before it")
-        assert bails <= unsettled + se.C_EDGE // 16, (i, nt)
+    with pairing.pair(cfg, dict(ticks_per_launch=TPL), threads=1) as (g, r):
+        launch(g, r, 300 * P, "election launch", "always")
+        launch(g, r, 2 * P, f"launch of {2 * P}", "always")
+        for i, nt in enumerate([1] * (2 * P + 2) + [P - 1, P + 1, 3 * P + 1]):
+            unsettled = se.settled(r)[0]
+            for c in REWRITTEN:
+                se.leader_of(r, c)                   # settled: at the fixed point, in some phase
+                for be in (g, r):
+                    be.write_nodes(c, be.read_nodes_raw(c, 1))
+            launch(g, r, nt, f"launch {i} of {nt}", "always")
+            bails = g.diag_last_bails()
+            print(f"N={nodes} launch {i} of {nt}: bails {bails}, oracle unsettled {unsettled} "
+                  "before it")
+            assert bails <= unsettled + se.C_EDGE // 16, (i, nt)
 
 
 @pytest.mark.parametrize("variant", ["Q2F", "Q2F-1"])
@@ -154,8 +141,6 @@ def test_first_launch_cuts_the_election(nodes, d, variant, monkeypatch):
     cfg, P = se.edge_cfg(nodes, d, variant)
     F = nodes - 1
     for nt in range(P, 2 * P + 4 * d + 2 * F + 3):
-        g, r = pair(cfg)
-        launch(g, r, nt, f"first launch of {nt}", "always")
-        launch(g, r, 3 * P, f"launch of {3 * P} after a first one of {nt}", "always")
-        g.close()
-        r.close()
+        with pairing.pair(cfg, dict(ticks_per_launch=TPL), threads=1) as (g, r):
+            launch(g, r, nt, f"first launch of {nt}", "always")
+            launch(g, r, 3 * P, f"launch of {3 * P} after a first one of {nt}", "always")

@@ -6,58 +6,12 @@ import numpy as np
 import pytest
 
 import helpers
+import pairing
+from cases import C_CUT, cut_cfg
 from raftsim import _abi
+from steady_pair import elected, step
 
 pytestmark = pytest.mark.gpu
-
-C_CUT = 199          # three full waves and a partial one: the shard ends inside a wave
-
-
-def cut_cfg(nodes, d, clusters=C_CUT):
-    """Small timers on which the certified path's conditions hold (hb >= 2d + F, el_base >= P)
-    and a launch end can land in every phase of a round."""
-    F = nodes - 1
-    hb = 2 * d + F + 2
-    P = 2 * d + F - 1 + hb
-    return dict(n_clusters=clusters, nodes=nodes, seed=100 + 10 * nodes + d, hb=hb, el_base=2 * P,
-                el_span=4 * P, dmin=d, dmax=d), P
-
-
-def same(g, r, what):
-    bad = np.nonzero(g.digest() != r.digest())[0]
-    assert not len(bad), (f"{what}: {len(bad)} clusters differ, first {bad[0]}:\n"
-                          + helpers.describe_cluster_diff(g, r, int(bad[0])))
-    assert g.counters() == r.counters(), what
-    gw, rw = g.read_nodes_raw(), r.read_nodes_raw()
-    if bytes(gw) == bytes(rw):
-        return
-    gn, rn = [n.as_dict(g.N) for n in gw], [n.as_dict(r.N) for n in rw]
-    for i, (x, y) in enumerate(zip(gn, rn)):
-        assert x == y, f"{what}: cluster {i // g.N} node {i % g.N + 1}: {x} != {y}"
-
-
-def both(g, r, n, what):
-    g.step(n)
-    r.step(n)
-    same(g, r, what)
-
-
-def elected(g, r, P):
-    """One long step: every cluster elects its leader and settles on its heartbeat schedule."""
-    both(g, r, 300 * P, "election step")
-    nodes = r.read_nodes()
-    N = r.N
-    for c in range(r.C):
-        cl = nodes[c * N:(c + 1) * N]
-        lead = [n for n in cl if n["role"] == 2]
-        assert len(lead) == 1 and all(n["role"] == 3 and n["current_term"] == lead[0]["current_term"]
-                                      for n in cl if n["role"] != 2), f"cluster {c} not settled"
-    # The elections' bails send auto mode through its cool-down: the launch after next reports
-    # them, then two launches take the general kernel. Six launches later the steady kernel runs
-    # every launch (a cluster off the fixed point's schedule may still be bailed in each).
-    for i in range(6):
-        both(g, r, 1, f"settle {i}")
-    assert g.diag_last_bails() >= 0, "the steady kernel does not run after the elections"
 
 
 @pytest.mark.parametrize("d", [1, 2, 3])
@@ -67,25 +21,23 @@ def test_every_cut_phase(nodes, d):
     append-entries in flight, each count of responses cut. 3P single-tick launches, then launches
     of P - 1, P, P + 1 and 7P + 3 ticks. Every launch takes the steady kernel."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for i in range(3 * P):
-        both(g, r, 1, f"single tick {i}")
-        assert g.diag_last_bails() >= 0, i
-    for nt in (P - 1, P, P + 1, 7 * P + 3):
-        both(g, r, nt, f"launch of {nt}")
-        assert g.diag_last_bails() >= 0, nt
+    with pairing.pair(cfg, threads=1) as (g, r):
+        elected(g, r, P)
+        for i in range(3 * P):
+            step(g, r, 1, f"single tick {i}")
+            assert g.diag_last_bails() >= 0, i
+        for nt in (P - 1, P, P + 1, 7 * P + 3):
+            step(g, r, nt, f"launch of {nt}")
+            assert g.diag_last_bails() >= 0, nt
 
 
 def test_default_timers():
     """The headline's shape at 1/16 size: default timers, six 10,000-tick steps, three of 1,000."""
     cfg = dict(n_clusters=4096, nodes=5, seed=42)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r, True)
-    for i, nt in enumerate([10000] * 6 + [1000] * 3):
-        both(g, r, nt, f"step {i} of {nt}")
-    assert g.diag_last_bails() == 0
+    with pairing.pair(cfg, idle_skip=True) as (g, r):
+        for i, nt in enumerate([10000] * 6 + [1000] * 3):
+            step(g, r, nt, f"step {i} of {nt}")
+        assert g.diag_last_bails() == 0
 
 
 def _leader(be, c):
@@ -135,27 +87,27 @@ def test_certificate_cleared(nodes, d, op, general_first):
     follows a launch of the general kernel (auto mode's cool-down after many bails, provoked by
     timing out a follower in each of 20 clusters), whose write-back clears certificates too."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    elected(g, r, P)
-    if general_first:
-        for be in (g, r):
-            for c in range(20, 40):
-                _op_nodes_deadline(be, c)
-        seen = False
-        for i in range(10):
-            both(g, r, 1, f"cool-down {i}")
-            if g.diag_last_bails() < 0:
-                seen = True
-                break
-        assert seen, "no launch took the general kernel"
-    for phase in range(P + 1):
-        c = (37 * phase + 5) % C_CUT
-        for be in (g, r):
-            OPS[op](be, c)
-        both(g, r, 1, f"{op} at phase {phase}")
-    for i in range(2 * P):
-        both(g, r, 1, f"after {i}")
-    both(g, r, 3 * P + 1, "long launch after")
+    with pairing.pair(cfg, threads=1) as (g, r):
+        elected(g, r, P)
+        if general_first:
+            for be in (g, r):
+                for c in range(20, 40):
+                    _op_nodes_deadline(be, c)
+            seen = False
+            for i in range(10):
+                step(g, r, 1, f"cool-down {i}")
+                if g.diag_last_bails() < 0:
+                    seen = True
+                    break
+            assert seen, "no launch took the general kernel"
+        for phase in range(P + 1):
+            c = (37 * phase + 5) % C_CUT
+            for be in (g, r):
+                OPS[op](be, c)
+            step(g, r, 1, f"{op} at phase {phase}")
+        for i in range(2 * P):
+            step(g, r, 1, f"after {i}")
+        step(g, r, 3 * P + 1, "long launch after")
 
 
 @pytest.mark.parametrize("nodes,d", [(5, 1), (5, 3), (4, 2)])
@@ -163,14 +115,14 @@ def test_mixed_waves(nodes, d):
     """One host-written cluster in each wave before a step: the wave leaves the line-0 path, and its
     other 63 clusters come out as the oracle's."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for phase in range(P + 2):
-        for be in (g, r):
-            for c in (7, 64 + 63, 128, C_CUT - 1):
-                _op_nodes_same(be, c)
-        both(g, r, 1 if phase % 3 else P + 1, f"phase {phase}")
-    both(g, r, 5 * P, "after")
+    with pairing.pair(cfg, threads=1) as (g, r):
+        elected(g, r, P)
+        for phase in range(P + 2):
+            for be in (g, r):
+                for c in (7, 64 + 63, 128, C_CUT - 1):
+                    _op_nodes_same(be, c)
+            step(g, r, 1 if phase % 3 else P + 1, f"phase {phase}")
+        step(g, r, 5 * P, "after")
 
 
 def _reserved(be):
@@ -185,20 +137,20 @@ def test_reserved_words_invisible():
     cfg = dict(n_clusters=1024, nodes=5, seed=9)
     a = helpers.gpu(**cfg, ticks_per_launch=30000)
     b = helpers.gpu(**cfg, ticks_per_launch=1000)
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r, True)
-    a.step(30000)
-    for _ in range(30):
-        b.step(1000)
-    r.step(30000)
-    assert a.diag_last_bails() >= 0 and b.diag_last_bails() == 0
-    assert not _reserved(a).any() and not _reserved(b).any()
-    assert (a.digest() == b.digest()).all() and (a.digest() == r.digest()).all()
-    assert a.counters() == b.counters() == r.counters()
+    r = pairing.oracle(cfg, idle_skip=True)
+    with pairing.closing(a, b, r):
+        a.step(30000)
+        for _ in range(30):
+            b.step(1000)
+        r.step(30000)
+        assert a.diag_last_bails() >= 0 and b.diag_last_bails() == 0
+        assert not _reserved(a).any() and not _reserved(b).any()
+        assert (a.digest() == b.digest()).all()
+        pairing.same(a, r, "one launch of 30000")
+        assert b.counters() == pairing.same_counters(a, r)
     cfg2, P = cut_cfg(4, 1)
-    g, r2 = helpers.gpu(**cfg2), helpers.oracle(**cfg2)
-    elected(g, r2, P)
-    for i in range(P):
-        both(g, r2, 1, f"tick {i}")
-        assert not _reserved(g).any()
+    with pairing.pair(cfg2, threads=1) as (g, r2):
+        elected(g, r2, P)
+        for i in range(P):
+            step(g, r2, 1, f"tick {i}")
+            assert not _reserved(g).any()

@@ -6,8 +6,9 @@ after every launch: digests, counters, every node record."""
 import numpy as np
 import pytest
 
-import helpers
-from test_gpu_steady_line0 import both, cut_cfg, elected, same  # noqa: F401
+import pairing
+from cases import cut_cfg
+from steady_pair import elected, step
 
 pytestmark = pytest.mark.gpu
 
@@ -31,15 +32,15 @@ def test_every_leader_position_every_phase(nodes, d):
     holds whole rounds and is cut at both ends), then P + 2 launches of 2P - 1 ticks (the phase moves
     the other way, and K takes both values of the band within a wave)."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    elected(g, r, P)
-    lead = leaders_by_position(r)
-    print("clusters led by each node position:", lead.tolist())
-    assert lead.sum() == r.C and (lead >= 20).all(), lead
-    for nt in (P + 1, 2 * P - 1):
-        for i in range(P + 2):
-            both(g, r, nt, f"launch {i} of {nt} ticks")
-            assert g.diag_last_bails() >= 0, (nt, i)
+    with pairing.pair(cfg, threads=1) as (g, r):
+        elected(g, r, P)
+        lead = leaders_by_position(r)
+        print("clusters led by each node position:", lead.tolist())
+        assert lead.sum() == r.C and (lead >= 20).all(), lead
+        for nt in (P + 1, 2 * P - 1):
+            for i in range(P + 2):
+                step(g, r, nt, f"launch {i} of {nt} ticks")
+                assert g.diag_last_bails() >= 0, (nt, i)
 
 
 @pytest.mark.parametrize("nodes,d", [(5, 1), (2, 2)])
@@ -48,23 +49,21 @@ def test_no_append_entries_in_the_launch(nodes, d):
     go back as loaded. Half way, clusters 0 and 198 are written with their own records: their
     waves leave the line-0 body for a launch and come back to it."""
     cfg, P = cut_cfg(nodes, d)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    elected(g, r, P)
-    for i in range(2 * P):
-        if i == P:
-            for be in (g, r):
-                for c in (0, 198):
-                    be.write_nodes(c, be.read_nodes_raw(c, 1))
-        both(g, r, 1, f"single tick {i}")
-        assert g.diag_last_bails() >= 0, i
+    with pairing.pair(cfg, threads=1) as (g, r):
+        elected(g, r, P)
+        for i in range(2 * P):
+            if i == P:
+                for be in (g, r):
+                    for c in (0, 198):
+                        be.write_nodes(c, be.read_nodes_raw(c, 1))
+            step(g, r, 1, f"single tick {i}")
+            assert g.diag_last_bails() >= 0, i
 
 
 def test_default_timers_small():
     """The headline's own stream, 256 clusters: five launches of 10,000 ticks, no bail at the end."""
     cfg = dict(n_clusters=256, nodes=5, seed=42)
-    g, r = helpers.gpu(**cfg), helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r, True)
-    for i in range(5):
-        both(g, r, 10000, f"step {i}")
-    assert g.diag_last_bails() == 0
+    with pairing.pair(cfg, idle_skip=True) as (g, r):
+        for i in range(5):
+            step(g, r, 10000, f"step {i}")
+        assert g.diag_last_bails() == 0

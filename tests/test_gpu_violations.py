@@ -15,9 +15,10 @@ import numpy as np
 import pytest
 
 import helpers
+import pairing
 import raftsim
+from cases import CASES
 from raftsim import dist
-from test_gpu_parity import CASES
 from viol_oracle import KINDS, as_records, expected_records, expected_window
 
 pytestmark = pytest.mark.gpu
@@ -72,8 +73,7 @@ def test_sums_and_minimum_are_the_counters(small_runs, name):
 @pytest.mark.parametrize("name", ["burst_variant_mid_n8", "fast_timers"])
 def test_state_is_untouched(small_runs, name):
     """No record write lands in state: every cluster's digest is the oracle's after the run."""
-    r = helpers.oracle(**small_cfg(name))
-    helpers.oracle_threads(r, helpers.cpu_threads())
+    r = pairing.oracle(small_cfg(name))
     r.step(STEPS[-1])
     assert np.array_equal(small_runs[name]["digest"], r.digest())
     assert small_runs[name]["seen"][-1][1] == r.counters()

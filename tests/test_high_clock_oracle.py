@@ -15,7 +15,7 @@ import census_oracle
 import helpers
 import high_clock as hc
 import pyref
-import test_gpu_high_clock as gpu_cases
+from cases import GENERAL, HC_CHUNKS, LITE, QUERIES, TRACED, lite_cfg
 
 TICKS = 600
 # 4 clusters, N = 5, with every fault, the bursty client and the trace rings
@@ -93,7 +93,7 @@ def test_bases():
 @pytest.mark.parametrize("cfg", [
     dict(n_clusters=4, nodes=5, seed=1),
     dict(BASE, hb=300),
-    dict(gpu_cases.GENERAL["clients_n5"], n_clusters=8),
+    dict(GENERAL["clients_n5"], n_clusters=8),
 ], ids=["default_timers", "hb_longest", "clients_n5"])
 def test_the_horizon(cfg):
     """A step that ends exactly at last_end(cfg) is accepted; one more tick is refused with the
@@ -114,7 +114,7 @@ def test_the_horizon(cfg):
 KEYS = ("leaders", "ev_timeout", "delivered", "overflow", "partitioned", "duplicated", "dropped",
         "client_injected", "redirects", "entries_appended", "viol_election", "viol_log",
         "viol_complete")
-WITNESSED = dict(gpu_cases.GENERAL, **gpu_cases.TRACED, **gpu_cases.QUERIES)
+WITNESSED = dict(GENERAL, **TRACED, **QUERIES)
 # The counters KEYS of the oracle after the 6,000 ticks of each case, per base in the order of
 # high_clock.BASES, measured on the CPU (no figure here comes from a GPU). A counter the
 # configuration leaves off is 0. period_2p31 at TOP injects nothing: its next window starts past
@@ -280,7 +280,7 @@ LITE_N6 = ("lite_n6", "lite_n7_d4", "lite_n9", "spec_lite_n6_elections")
 
 def witness_run(cfg, base, chunks):
     T0 = hc.base_tick(base, cfg, sum(chunks))
-    r = hc.start(gpu_cases.oracle, cfg, T0)
+    r = hc.start(hc.oracle, cfg, T0)
     for n in chunks:
         r.step(n)
     c = r.counters()
@@ -293,7 +293,7 @@ def witness_run(cfg, base, chunks):
 def test_general_cases_are_not_trivial(name):
     cfg = WITNESSED[name]
     for base, measured in zip(hc.BASES, MEASURED[name]):
-        c, one = witness_run(cfg, base, gpu_cases.CHUNKS)
+        c, one = witness_run(cfg, base, HC_CHUNKS)
         print(name, base, tuple(c[k] for k in KEYS), one)
         for k, m in zip(KEYS, measured):
             assert c[k] >= m // 2, (base, k, c[k], m)
@@ -301,13 +301,13 @@ def test_general_cases_are_not_trivial(name):
         assert c["ev_timeout"] >= cfg["n_clusters"] and c["delivered"] > 0
         if name in LITE_N6:
             assert 2 * one >= cfg["n_clusters"], (base, one)
-        if name in gpu_cases.QUERIES:
+        if name in QUERIES:
             assert c["viol_election"] + c["viol_log"] + c["viol_complete"] >= 16, base
 
 
-@pytest.mark.parametrize("nodes,d", gpu_cases.LITE)
+@pytest.mark.parametrize("nodes,d", LITE)
 def test_lite_plans_settle(nodes, d):
-    cfg, P, plan = gpu_cases.lite_cfg(nodes, d)
+    cfg, P, plan = lite_cfg(nodes, d)
     for base, measured in zip(hc.BASES, LITE_MEASURED[nodes, d]):
         c, one = witness_run(cfg, base, plan)
         got = (c["leaders"], c["ev_timeout"], c["delivered"], one)

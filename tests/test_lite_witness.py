@@ -16,8 +16,8 @@ No figure here comes from the GPU.
 """
 import pytest
 
-import helpers
-from test_gpu_parity import CASES
+import pairing
+from cases import CASES
 
 MEASURED = {
     "lite_n6": dict(leaders=700, ev_heartbeat=44000),
@@ -41,8 +41,7 @@ def test_case_reaches_its_states(name):
     # fault-free, client-free, fixed delay: DevSim::lite is set
     assert not any(cfg.get(k) for k in ("client_ppm", "drop_ppm", "dup_ppm", "part_ppm"))
     assert cfg.get("dmin", 1) == cfg.get("dmax", 1)
-    r = helpers.oracle(**cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
+    r = pairing.oracle(cfg)
     r.step(20000)
     c = r.counters()
     r.close()

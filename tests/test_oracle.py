@@ -5,6 +5,7 @@ import random
 import pytest
 
 import helpers
+import pairing
 import pyref
 
 KAT = [((0, 0, 0, 0), (0, 0), (0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8)),
@@ -109,11 +110,8 @@ def test_spec_raft_is_safe_and_the_injected_bug_is_not(nodes):
     stale candidate win and lose committed entries (leader completeness)."""
     base = dict(n_clusters=512, nodes=nodes, seed=5, client_ppm=10000, log_cap=512, hb=300,
                 el_base=500, el_span=500, **FAULTS)
-    ctl = helpers.oracle(variant_flags=2, **base)
-    bug = helpers.oracle(variant_flags=3, **base)
-    for be in (ctl, bug):
-        helpers.oracle_threads(be, helpers.cpu_threads())
-        be.step(30000)
+    ctl = pairing.oracle(dict(base, variant_flags=2), ticks=30000)
+    bug = pairing.oracle(dict(base, variant_flags=3), ticks=30000)
     c, b = ctl.counters(), bug.counters()
     assert c["leaders"] > 1000 and c["entries_applied"] > 10000
     assert c["viol_election"] == c["viol_log"] == c["viol_complete"] == 0

@@ -9,9 +9,10 @@ import pytest
 import gather_mirror as gm
 import helpers
 import hostprog
+import pairing
 import raftsim
+from cases import ROUNDTRIP
 from raftsim import _abi, _build
-from test_gather_abi import ROUNDTRIP, run_oracle
 
 HEADER = (hostprog.ROOT / "include" / "raftsim.h").read_text()
 CLJ = (hostprog.ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
@@ -76,13 +77,13 @@ def test_bad_arguments_are_refused_without_a_device():
 
 
 def test_python_refusals_before_any_handle():
-    h = run_oracle(dict(ROUNDTRIP, n_clusters=4), 100)
+    h = pairing.oracle(dict(ROUNDTRIP, n_clusters=4), threads=8, ticks=100)
     for missing in _abi.SCATTER_PARTS:
         pack = gm.pack_of(h, [0, 1], [p for p in gm.PARTS if p != missing])
         for call in (lambda: raftsim.resume(pack), lambda: raftsim.fan_out(pack, 0, 8)):
             with pytest.raises(ValueError, match=f"needs the '{missing}' part"):
                 call()
-    s = run_oracle(dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4), 100)
+    s = pairing.oracle(dict(ROUNDTRIP, n_clusters=1, commit_stream_cap=4), threads=8, ticks=100)
     with pytest.raises(ValueError, match="'streams'"):
         raftsim.resume(gm.pack_of(s, [0], gm.PARTS[:-1]))
     # a pack resumes as a run of consecutive ascending ids only
@@ -107,7 +108,8 @@ def test_python_refusals_before_any_handle():
 
 def test_fan_out_past_the_last_global_id_is_the_configs_error():
     """g + copies > 2^32: raft_sim_create's own refusal, which precedes every device call."""
-    h = run_oracle(dict(ROUNDTRIP, n_clusters=2, cluster_offset=2 ** 32 - 2), 100)
+    h = pairing.oracle(dict(ROUNDTRIP, n_clusters=2, cluster_offset=2 ** 32 - 2), threads=8,
+                       ticks=100)
     pack = gm.pack_of(h, [1])
     assert pack.global_ids == [2 ** 32 - 1]
     with pytest.raises(raftsim.RaftSimError, match=r"cluster_offset \+ n_clusters"):

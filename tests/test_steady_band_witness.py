@@ -11,8 +11,9 @@ band's edges fails here, without a GPU.
 import pytest
 
 import helpers
+import pairing
 import steady_band as sb
-from test_gpu_steady_line0 import cut_cfg
+from cases import cut_cfg
 
 
 def settle(r, P):
@@ -26,8 +27,7 @@ def settle(r, P):
 @pytest.mark.parametrize("nodes", [2, 3, 4, 5])
 def test_clusters_on_both_sides_of_rho(nodes, d):
     cfg, P = sb.band_cfg(nodes, d)
-    with helpers.oracle(**cfg) as r:
-        helpers.oracle_threads(r, helpers.cpu_threads())
+    with pairing.oracle(cfg) as r:
         settle(r, P)
         for nt in sb.rho_launches(nodes, d, P):
             dl = sb.deltas(r, d, cfg["hb"], P)
@@ -43,8 +43,7 @@ def test_clusters_on_both_sides_of_rho(nodes, d):
 @pytest.mark.parametrize("nodes,d", [(5, 2), (3, 1)])
 def test_a_cluster_at_the_bands_last_value(nodes, d):
     cfg, P = cut_cfg(nodes, d)
-    with helpers.oracle(**cfg) as r:
-        helpers.oracle_threads(r, helpers.cpu_threads())
+    with pairing.oracle(cfg) as r:
         settle(r, P)
         dl = sb.deltas(r, d, cfg["hb"], P)
         print(f"N={nodes} d={d}: {dl.count(P - 1)} clusters at delta = P - 1")

@@ -20,6 +20,7 @@ independent Python restatement (oracle/pyref.py) on the same edges.
 import pytest
 
 import helpers
+import pairing
 import pyref
 import steady_edges as se
 
@@ -30,8 +31,7 @@ def run_witness(nodes, d, variant):
     """(unsettled, led, follower_ties, leader_ties): a 300P step, then 2P single ticks with the
     ties summed before each."""
     cfg, P = se.edge_cfg(nodes, d, variant)
-    with helpers.oracle(**cfg) as r:
-        helpers.oracle_threads(r, helpers.cpu_threads())
+    with pairing.oracle(cfg) as r:
         r.step(300 * P)
         unsettled, led = se.settled(r)
         fol = lead = 0

@@ -9,11 +9,12 @@ import pytest
 
 import helpers
 import hostprog
+import pairing
 import raftsim
 import viol_oracle
+from cases import CASES, GENERAL
 from hostprog import HEADER, ROOT
 from raftsim import _abi, _backend
-from test_gpu_parity import CASES
 
 CLJ = (ROOT / "clojure" / "src" / "raft" / "sim.clj").read_text()
 
@@ -117,8 +118,7 @@ def test_one_cluster_handles_sum_to_the_whole_handle():
     cfg = dict(CASES["burst_variant_mid_n8"], n_clusters=96)
     steps = (5000, 10000, 15000, 20000)
     per_step = viol_oracle.expected_records(cfg, 96, steps)
-    whole = helpers.oracle(**cfg)
-    helpers.oracle_threads(whole, helpers.cpu_threads())
+    whole = pairing.oracle(cfg)
     for t, exp in zip(steps, per_step):
         whole.step(t - whole.tick)
         c = whole.counters()
@@ -140,7 +140,6 @@ def test_one_cluster_handles_sum_to_the_whole_handle_across_2_31():
     last two at and above 2^31. (Measured at 96 clusters: election 18 / log 295 / complete 11 at
     the end, first tick 2147481308.)"""
     import high_clock as hc
-    from test_gpu_high_clock import GENERAL
 
     cfg = dict(GENERAL["variant1_n5"], n_clusters=96)
     T0 = hc.SIGN(6000)
