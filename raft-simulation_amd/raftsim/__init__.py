@@ -52,37 +52,6 @@ class Simulator(GpuBackend):
         check_build()
         super().__init__(LIB_PATH, "raft_sim_", **config)
 
-    def diag_last_bails(self):
-        """Diagnostic: clusters the steady kernel handed to the general kernel in the last tick
-        launch (steady_kernel.hip), or -1 if that launch did not take the steady path."""
-        import ctypes
-
-        f = self._lib.raftsim_diag_last_bails
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p]
-        return int(f(self._h))
-
-    def diag_storm_bails(self):
-        """Diagnostic: clusters the storm kernel (storm_kernel.hip) listed for the lane-per-node
-        STORM body in the last storm launch, summed over shards; -1 if no storm-kernel launch ran
-        on this handle."""
-        import ctypes
-
-        f = self._lib.raftsim_diag_storm_bails
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p]
-        return int(f(self._h))
-
-    def timed_launches(self):
-        """Launches of the last sync window that carried HIP events: last_step_timing's average
-        is over these (every general launch, the first steady launch after a sync)."""
-        import ctypes
-
-        f = self._lib.raftsim_last_timed_launches
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p]
-        return int(f(self._h))
-
 
 def replay(sim, cluster, ticks=None):
     """A one-cluster Simulator that reruns cluster `cluster` of `sim` with the trace rings on

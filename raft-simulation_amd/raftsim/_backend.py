@@ -484,6 +484,31 @@ class GpuBackend(Backend):
         self._check(f(self._h, C.byref(ms)))
         return ms.value
 
+    def diag_last_bails(self):
+        """Diagnostic: clusters the steady kernel handed to the general kernel in the last tick
+        launch (steady_kernel.hip), or -1 if that launch did not take the steady path."""
+        f = self._lib.raftsim_diag_last_bails
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        return int(f(self._h))
+
+    def diag_storm_bails(self):
+        """Diagnostic: clusters the storm kernel (storm_kernel.hip) listed for the lane-per-node
+        STORM body in the last storm launch, summed over shards; -1 if no storm-kernel launch ran
+        on this handle."""
+        f = self._lib.raftsim_diag_storm_bails
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        return int(f(self._h))
+
+    def timed_launches(self):
+        """Launches of the last sync window that carried HIP events: last_step_timing's average
+        is over these (every general launch, the first steady launch after a sync)."""
+        f = self._lib.raftsim_last_timed_launches
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        return int(f(self._h))
+
     def violations(self, kinds=("election", "log", "complete"), t_lo=0, t_hi=None, limit=None):
         """The clusters the checker counted a violation for: (total, records). A cluster matches
         when it has a violation of one of `kinds` and its first violation tick lies in

@@ -13,33 +13,18 @@ c5      config 5: config 3's faults and client with the vote granted without the
         clusters (all host threads, idle-tick skipping), bit-exactness, and the Spec-Raft control
         (flag 2) run for as many ticks: leaders, commits, violations.
 GPU rates are node-ticks/s over steps of 10k ticks after a warm-up (state resident in HBM)."""
-import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path[:0] = [str(ROOT / "raft-simulation_amd"), str(ROOT / "tests"), str(ROOT / "oracle")]
-import helpers  # noqa: E402
-import raftsim  # noqa: E402
-
-FAULTS = dict(drop_ppm=100000, dup_ppm=10000, dmin=1, dmax=50, part_ppm=100000)
-C3 = dict(nodes=5, seed=1, client_ppm=80000, client_period=16384, client_burst=2048,
-          client_redirects=4, log_cap=256, **FAULTS)
-C4 = dict(log_cap=4096, client_ppm=500000, client_period=8192, client_burst=2048,
-          client_redirects=4)
-
-
-def emit(rec):
-    print(json.dumps(rec), flush=True)
+import probe
+from probe import emit
+import helpers  # noqa: E402  (tests/: on the path once probe is imported)
+import pairing  # noqa: E402
 
 
 def cpu_oracle(cfg, clusters, ticks_list):
-    r = helpers.oracle(n_clusters=clusters, **cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r)
+    r = pairing.oracle(dict(cfg, n_clusters=clusters), idle_skip=True)
     dts = []
     for t in ticks_list:
         t0 = time.perf_counter()
@@ -58,8 +43,9 @@ def node_census(sim):
 
 
 def c3_shard():
-    n, clusters = 5, 131072
-    g = raftsim.Simulator(n_clusters=clusters, **C3)
+    C3 = probe.workload("c3")
+    n, clusters = C3["nodes"], C3["n_clusters"]
+    g = probe.open_sim(**C3)
     g.step(20000)
     t0 = time.perf_counter()
     for _ in range(4):
@@ -73,16 +59,12 @@ def c3_shard():
           "gpu_counters": {k: v for k, v in g.counters().items() if v}, **node_census(g)})
 
 
-def c4(name, nodes, seed, variant=0, clusters=16384, total=110000):
-    cfg = dict(nodes=nodes, seed=seed, variant_flags=variant, **C4)
-    g = raftsim.Simulator(n_clusters=clusters, **cfg)
-    steps, kms = [], []
+def c4(name, workload, total=110000):
+    cfg = probe.workload(workload)
+    nodes, clusters, variant = cfg["nodes"], cfg["n_clusters"], cfg.setdefault("variant_flags", 0)
+    g = probe.open_sim(**cfg)
     t_all = time.perf_counter()
-    for s in range(total // 10000):
-        t0 = time.perf_counter()
-        g.step(10000)
-        steps.append(time.perf_counter() - t0)
-        kms.append(g.last_step_timing()[0])
+    kms = [launch.ms for launch in probe.launches(g, total // probe.TICKS)]
     gdt = time.perf_counter() - t_all
     cpu_n = 512
     r, dts = cpu_oracle(cfg, cpu_n, [total])
@@ -107,13 +89,12 @@ def first_violation(sim, chunk, max_ticks):
     return None, done, time.perf_counter() - t0
 
 
-def time_to_violation(name, flags, clusters=131072, chunk=1000, max_ticks=200000):
-    cfg = dict(C3, variant_flags=flags)
-    g = raftsim.Simulator(n_clusters=clusters, **cfg)
+def time_to_violation(name, flags, chunk=1000, max_ticks=200000):
+    cfg = probe.workload("c3", variant_flags=flags)
+    clusters = cfg["n_clusters"]
+    g = probe.open_sim(**cfg)
     gfv, gdone, gdt = first_violation(g, chunk, max_ticks)
-    r = helpers.oracle(n_clusters=clusters, **cfg)
-    helpers.oracle_threads(r, helpers.cpu_threads())
-    helpers.oracle_idle_skip(r)
+    r = pairing.oracle(cfg, idle_skip=True)
     cfv, cdone, cdt = first_violation(r, chunk, gdone)
     emit({"config": name, "variant_flags": flags, "clusters": clusters,
           "first_violation_tick": gfv, "ticks_simulated": gdone, "gpu_wall_s": gdt,
@@ -123,22 +104,24 @@ def time_to_violation(name, flags, clusters=131072, chunk=1000, max_ticks=200000
     return gdone
 
 
-def main():
-    names = sys.argv[1:] or ["c3", "c4", "c5"]
+def main(argv=None):
+    p = probe.parser(__doc__)
+    p.add_argument("names", nargs="*", metavar="CONFIG", help="of c3, c4, c5 (default: all)")
+    names = p.parse_args(argv).names or ["c3", "c4", "c5"]
     if "c3" in names:
         c3_shard()
     if "c4" in names:
-        c4("c4_n7", 7, 3)
-        c4("c4_n9", 9, 5)
-        c4("c4_spec_n9", 9, 5, variant=2)
+        c4("c4_n7", "c4_n7")
+        c4("c4_n9", "c4_n9")
+        c4("c4_spec_n9", "c4_spec")
     if "c5" in names:
         ticks = time_to_violation("c5_faithful_nolog", 1)
         ticks = max(ticks, time_to_violation("c5_spec_nolog", 3))
-        ctl = raftsim.Simulator(n_clusters=131072, **dict(C3, variant_flags=2))
+        ctl = probe.open_sim(**probe.workload("c3", variant_flags=2))
         t0 = time.perf_counter()
         ctl.step(ticks)
         c = ctl.counters()
-        emit({"config": "c5_spec_control", "variant_flags": 2, "clusters": 131072,
+        emit({"config": "c5_spec_control", "variant_flags": 2, "clusters": ctl.C,
               "ticks_simulated": ticks, "gpu_wall_s": time.perf_counter() - t0,
               "first_violation_tick": c["first_violation_tick"], "leaders": c["leaders"],
               "entries_applied": c["entries_applied"],

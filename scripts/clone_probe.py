@@ -9,31 +9,13 @@ second handle), and for the first 4,096 pairs of the respawn the host path, scat
 Per measurement: kernel ms (raftsim_diag_clone_ms; the gather's plus the scatter's for the host
 path) and wall ms around the call, best of the last three of four calls, and GB/s of state written
 (the stride of the record a scatter needs, per target). One JSON line per measurement."""
-import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path[:0] = [str(ROOT / "raft-simulation_amd"), str(ROOT / "scripts")]
-import raftsim  # noqa: E402
+from probe import best, emit, open_sim, parser, workload
+import raftsim  # noqa: E402  (on the path once probe is imported)
 from raftsim import _abi  # noqa: E402
-from bench_configs import C3  # noqa: E402
-
-
-def emit(rec):
-    print(json.dumps(rec), flush=True)
-
-
-def best(fn, calls=4, keep=3):
-    out = []
-    for _ in range(calls):
-        t0 = time.perf_counter()
-        ms = fn()
-        out.append((ms, (time.perf_counter() - t0) * 1e3))
-    return min(k for k, _ in out[-keep:]), min(w for _, w in out[-keep:])
 
 
 def report(what, n, stride, kernel, wall):
@@ -51,8 +33,14 @@ def clone_cost(what, dst, sources, targets, stride, source=None):
     report(what, len(targets), stride, *best(call))
 
 
-def main(clusters, ticks):
-    sim = raftsim.Simulator(n_clusters=clusters, **C3)
+def main(argv=None):
+    p = parser(__doc__)
+    p.add_argument("clusters", nargs="?", type=int, help="default: one GPU's shard of C3")
+    p.add_argument("ticks", nargs="?", type=int, default=20000)
+    args = p.parse_args(argv)
+    cfg = workload("c3", args.clusters)
+    clusters, ticks = cfg["n_clusters"], args.ticks
+    sim = open_sim(**cfg)
     for _ in range(ticks // 10000):
         sim.step_async(10000)
     sim.sync()
@@ -93,5 +81,4 @@ def main(clusters, ticks):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 131072,
-         int(sys.argv[2]) if len(sys.argv) > 2 else 20000)
+    main()

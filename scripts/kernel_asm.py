@@ -18,6 +18,7 @@ one difference is the name of the symbol __hip_cuid_<16 hex digits>, which clang
 file's path (five lines of each unit: .type, .globl, the label, .size, .addrsig_sym). Its digits
 are removed. The assembly has no .file directive, no path and no time.
 """
+import argparse
 import re
 import subprocess
 import sys
@@ -97,20 +98,26 @@ def diff(dir_a, dir_b):
     return 1 if differing else 0
 
 
-def main(argv):
-    if argv[:1] == ["diff"] and len(argv) == 3:
-        return diff(argv[1], argv[2])
-    if argv and (argv[0] != "--asm-dir" or len(argv) != 2):
-        sys.exit(__doc__)
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__,
+                                formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--asm-dir", metavar="DIR", help="keep the normalised assembly as DIR/<unit>.s")
+    p.add_argument("diff", nargs="*", metavar="diff DIR_A DIR_B",
+                   help="compare two --asm-dir runs instead of compiling")
+    args = p.parse_args(argv)
+    if args.diff:
+        if args.diff[0] != "diff" or len(args.diff) != 3 or args.asm_dir:
+            p.error("expected: diff DIR_A DIR_B")
+        return diff(*args.diff[1:])
     with ThreadPoolExecutor(JOBS) as pool:
         asm = dict(zip(_build.UNITS, pool.map(compile_unit, _build.UNITS)))
-    if argv:
-        Path(argv[1]).mkdir(parents=True, exist_ok=True)
+    if args.asm_dir:
+        Path(args.asm_dir).mkdir(parents=True, exist_ok=True)
         for unit, text in asm.items():
-            (Path(argv[1]) / (Path(unit).stem + ".s")).write_text(text)
+            (Path(args.asm_dir) / (Path(unit).stem + ".s")).write_text(text)
     print(table(asm))
     return 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:]))
+    sys.exit(main())

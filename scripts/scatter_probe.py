@@ -14,33 +14,14 @@ write_clusters, N x write_arena, 2N x write_queue, N x write_commit_stream) as b
 on views of the pack's bytes made beforehand, so that no Python conversion is timed. One JSON line
 per measurement. One process per handle."""
 import ctypes as C
-import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path[:0] = [str(ROOT / "raft-simulation_amd"), str(ROOT / "scripts")]
-import raftsim  # noqa: E402
-from raftsim import _abi  # noqa: E402
-from bench_configs import C3, C4  # noqa: E402
+from probe import best, emit, open_sim, parser, workload
+from raftsim import _abi  # noqa: E402  (on the path once probe is imported)
 
 PARTS = ("cluster", "nodes", "queues", "arenas", "streams")
-
-
-def emit(rec):
-    print(json.dumps(rec), flush=True)
-
-
-def best(fn, calls=4, keep=3):
-    out = []
-    for _ in range(calls):
-        t0 = time.perf_counter()
-        ms = fn()
-        out.append((ms, (time.perf_counter() - t0) * 1e3))
-    return min(k for k, _ in out[-keep:]), min(w for _, w in out[-keep:])
 
 
 def scatter_cost(name, sim, pack, clusters, records=None):
@@ -107,12 +88,15 @@ def write_loop(sim, pack):
     return calls, (time.perf_counter() - t0) * 1e3
 
 
-def main(which):
+def main(argv=None):
+    p = parser(__doc__)
+    p.add_argument("which", nargs="?", default="c3", choices=("c3", "c4_n9"))
+    which = p.parse_args(argv).which
     if which == "c3":
-        sim = raftsim.Simulator(n_clusters=131072, **C3)
+        sim = open_sim(**workload("c3"))
         ticks, take = 200000, 4096
     else:
-        sim = raftsim.Simulator(n_clusters=1024, **dict(C4, nodes=9, seed=5))
+        sim = open_sim(**workload("c4_n9", 1024))
         ticks, take = 110000, 1024
     for _ in range(ticks // 10000):
         sim.step_async(10000)
@@ -140,4 +124,4 @@ def main(which):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "c3")
+    main()

@@ -91,7 +91,7 @@ def test_no_script_and_no_test_has_a_recipe_of_its_own():
     docstring, a comment, the C++ text of a check program -- builds nothing and is left alone. The
     stand-alone probes and the profile scripts that compile one of them are no part of the
     library."""
-    exempt = {"fetch_probe.hip", "p0_probe.hip", "launch_probe.hip", "profile.sh", "profile_all.sh"}
+    exempt = {"fetch_probe.hip", "p0_probe.hip", "launch_probe.hip", "profile_all.sh"}
     units = {Path(u).name for u in _build.UNITS}
     assert units == set(NAMES)
     files = [f for d in ("scripts", "tests") for f in sorted((ROOT / d).iterdir())
