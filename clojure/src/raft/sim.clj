@@ -358,6 +358,38 @@
     (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
     rc))
 
+(def restart-modes {:amnesia 0 :durable 1})
+
+(defn restart
+  "Nodes started again on the device at the handle's tick (raft_restart_write; SIM_SPEC §4a): node id
+  j of cluster (nth cs i) is restarted where bit j of (nth masks i) is set (as :votes). `mode` is
+  :amnesia (the reference's JVM started again: init-node and a fresh log, nothing read from disk) or
+  :durable (current-term, voted-for and the log survive: Raft's Figure 2). Both empty the node's
+  queues and re-arm its election timer from the current tick. A cluster may be named once. Returns
+  the number of nodes restarted."
+  [sim cs masks mode]
+  (let [n (count cs)
+        _ (when (not= n (count masks))
+            (throw (ex-info "restart: as many masks as clusters" {:clusters n :masks (count masks)})))
+        ints (Memory. (* 4 (max 1 n)))
+        shorts (Memory. (* 2 (max 1 n)))
+        _ (doseq [[i c] (map-indexed vector cs)] (.setInt ints (* 4 i) (unchecked-int c)))
+        _ (doseq [[i m] (map-indexed vector masks)] (.setShort shorts (* 2 i) (unchecked-short m)))
+        rc (.invokeLong (f "raft_restart_write")
+                        (object-array [(:ptr sim) ints shorts (int n) (int (restart-modes mode mode))]))]
+    (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
+    rc))
+
+(defn restart-where
+  "Every node of the handle whose fault code f has bit f set in `fault-mask` (1..31; bit 0 = the
+  running nodes, 1 IOOBE, 2 NPE, 3 CCE, 4 OVERFLOW) started again, found and counted on the device
+  in one pass (raft_restart_where). `mode` as in restart. Returns the number of nodes restarted."
+  [sim fault-mask mode]
+  (let [rc (.invokeLong (f "raft_restart_where")
+                        (object-array [(:ptr sim) (int fault-mask) (int (restart-modes mode mode))]))]
+    (when (neg? rc) (throw (ex-info (last-error) {:rc rc})))
+    rc))
+
 (defn digest
   "Per-cluster FNV-1a-64 of the canonical state (SIM_SPEC §6) for clusters [c0, c0+nc)."
   [sim c0 nc]

@@ -507,6 +507,52 @@ int64_t raft_scatter_write(raft_sim_t* sim, const uint32_t* clusters, const uint
 int64_t raft_clone_write(raft_sim_t* dst, const uint32_t* targets, raft_sim_t* src,
                          const uint32_t* sources, uint32_t n);
 
+/* ---- Node restarts (crash recovery as a fault model; none in the oracle) ---------------------
+ * A halted node's process started again, on the device, between launches at the handle's current
+ * tick T (raft_sim_tick). SIM_SPEC.md §4a is the specification; in short, for node k of a cluster
+ * with global id g:
+ *
+ * RAFT_RESTART_AMNESIA is what the reference does when its JVM is started again (init-node and a
+ * fresh log atom, nothing read back from disk): role 0, current_term 1, voted_for, leader_id,
+ * votes, ls_present, ls_keys, every next_index / match_index and fault 0; log_len, commit_index and
+ * entries_is_seq 0; arena_base = arena_frontier with the frontier kept, so no arena slot is touched
+ * and append-entries of this node still queued at peers keep a readable payload.
+ * RAFT_RESTART_DURABLE is the recovery of Raft's Figure 2 (not reference behaviour; legal under
+ * any variant): AMNESIA, except that current_term, voted_for and the whole log (log_len,
+ * arena_base, arena_frontier) are kept; commit_index becomes 0 (the state machine replays).
+ *
+ * Both empty the node's two queues (counts 0, head arrivals "never", rings restart at slot 0:
+ * messages queued or in flight to the node are gone) and arm the election timer with the INIT draw
+ * at tick T: deadline = T + el_base + (philox(g, k | INIT << 8, T, 0)[1] * el_span >> 32), exact.
+ * At T = 0 on a fresh handle an AMNESIA restart is the identity. Kept: commit_count and the
+ * commit-stream ring, trace_hash and the trace rings with their seq, last_led_term (the checker's
+ * memory). Of the cluster record only the reserved words become zero; hwm and the client cursor
+ * stay. Every other node, its queues and the messages it holds from the restarted node, counters,
+ * violation records and the clock are untouched.
+ *
+ * raft_restart_write: node id j of cluster clusters[i] is restarted where bit j of nodes[i] is set
+ * (as `votes` and raft_cluster_state_t.halted). Handle-local indices in any order, across shards.
+ * raft_restart_where: every node of the handle whose fault code f has bit f set in fault_mask
+ * (1..31; bit 0 = the running nodes), found and counted on the device in one pass over the hot
+ * blocks. Both return the number of nodes restarted.
+ *
+ * -EINVAL: a null sim, mode > 1; for raft_restart_write a null list with n > 0, an index >=
+ * n_clusters, a cluster named twice, a mask that is 0 or has bits outside ids 1..nodes (the message
+ * names the first offending position); for raft_restart_where fault_mask 0 or above 31. -ERANGE:
+ * T + el_base + el_span would reach 2^32 - 1. -EIO: a HIP error, or a poisoned handle. All refusals
+ * come before any device is touched: the call restarts everything or nothing. n == 0 returns 0 and
+ * launches nothing. Synchronous like the other writes: stream-ordered after everything enqueued
+ * (valid after raft_sim_step_async), then waited for. Only the list is uploaded, through the
+ * gather scratch (8 bytes a pair, 64 MiB per device at a time). */
+enum raft_restart_mode { RAFT_RESTART_AMNESIA = 0, RAFT_RESTART_DURABLE = 1 };
+
+/* nodes[i]: bit j = id j, as `votes` and raft_cluster_state_t.halted */
+int64_t raft_restart_write(raft_sim_t* sim, const uint32_t* clusters, const uint16_t* nodes,
+                           uint32_t n, uint32_t mode);
+
+/* every node whose fault code f has bit f set in fault_mask (1..31; bit 0 = running nodes) */
+int64_t raft_restart_where(raft_sim_t* sim, uint32_t fault_mask, uint32_t mode);
+
 #ifdef __cplusplus
 }
 #endif

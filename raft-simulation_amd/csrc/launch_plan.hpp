@@ -293,6 +293,10 @@ constexpr uint32_t ON_CLONE = ON_SCATTER;
 // ... and when a shard it reads from is no longer LITE: a cloned cluster may then carry a finite
 // client cursor or a queued client-set (no record is looked at on the host)
 constexpr uint32_t ON_CLONE_GENERAL = ON_SCATTER_GENERAL;
+// raft_restart_write, per touched shard, and raft_restart_where, every shard: what a scatter of the
+// same clusters marks, after every check (a refused restart has touched nothing). A restart only
+// removes queued client-sets and leaves the client cursor, so it never needs INV_LITE
+constexpr uint32_t ON_RESTART = ON_SCATTER;
 
 inline void invalidate(LaunchState& s, uint32_t what) {
   if (what & INV_STORM) s.storm_until = 0;

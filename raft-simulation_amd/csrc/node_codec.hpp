@@ -5,9 +5,10 @@
 //   hot_field   record -> hot block (raft_sim_write_nodes, scatter_kernel), FL_DRAW clear
 //   ring_words  what a queue ring contributes to the hot block (raft_sim_write_queue, scatter_kernel)
 //   hot_clone   hot block -> hot block (clone_kernel): hot_field of node_word without the record
+//   hot_restart hot block -> hot block (restart_kernel, restart_where_kernel): a node started again
 // Host and device: compiles for the CPU alone too (tests/test_node_codec_host.py checks the first
 // three against a by-member-name statement of the same mapping, tests/test_clone_host.py the fourth
-// against the first two).
+// against the first two, tests/test_restart_host.py the fifth against a restatement on the record).
 #pragma once
 #include <stddef.h>
 
@@ -185,6 +186,36 @@ __host__ __device__ __forceinline__ uint32_t queue_field(uint32_t f, uint32_t rq
 __host__ __device__ __forceinline__ uint32_t queue_field(uint32_t f, const RingWords& rq,
                                                          const RingWords& rs) {
   return queue_field_of(f, [&] { return rq; }, [&] { return rs; });
+}
+
+// Field f (< hot_fields(N)) of node k (id k + 1) of global cluster g after a restart at tick T
+// (include/raftsim.h, "Node restarts"; SIM_SPEC §4a) from the node's words before it. h: the node's
+// first hot word. mode 0 (RAFT_RESTART_AMNESIA) is init-node and a fresh log: role 0, term 1, no
+// vote, no leader, no fault, an empty log whose arena window starts at the frontier (no arena slot
+// is touched: payloads of this node still queued at peers stay readable). mode 1
+// (RAFT_RESTART_DURABLE) keeps current_term, voted_for and the log (len, base, frontier). Both
+// empty the two rings (queue_field of empty rings: head 0, count 0, arrival INF, tail 0), zero the
+// commit index, the masks and the peer rows, and arm the election timer with the INIT draw of tick
+// T, stored exact (FL_DRAW clear). The trace hash, the frontier and the last-led term are kept.
+__host__ __device__ __forceinline__ uint32_t hot_restart(const uint32_t* h, uint32_t N, uint32_t f,
+                                                         uint32_t mode, uint32_t T, uint32_t g,
+                                                         uint32_t k, const DrawKeys& dk) {
+  const bool durable = mode != 0;
+  if (hf_is_queue(f)) return queue_field(f, ring_words(0, 0, 0u, 0u), ring_words(1, 0, 0u, 0u));
+  if (f == hf_abase(N)) return h[(durable ? hf_abase(N) : hf_afront(N)) * N];
+  if (f == hf_afront(N) || f == hf_led(N)) return h[f * N];
+  switch (f) {
+    case HF_DEADLINE: {
+      const uint4 w = philox(g, (k + 1) | P_INIT << 8, T, 0, dk.key0, dk.key1);
+      return T + dk.el_base + (uint32_t)(((uint64_t)w.y * dk.el_span) >> 32);
+    }
+    case HF_TRACE_LO:
+    case HF_TRACE_HI: return h[f * N];
+    case HF_FLAGS: return pack_flags(0, durable ? fl_vf(h[HF_FLAGS * N]) : 0u, 0, 0, 0, 0);
+    case HF_TERM: return durable ? h[HF_TERM * N] : 1u;
+    case HF_LEN: return durable ? h[HF_LEN * N] : 0u;
+    default: return 0u;                                     // masks, commit index, next / match
+  }
 }
 
 }  // namespace rs

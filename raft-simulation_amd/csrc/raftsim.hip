@@ -10,6 +10,7 @@
 #include "clone_host.hpp"
 #include "launch_plan.hpp"
 #include "node_codec.hpp"
+#include "restart_host.hpp"
 #include "scatter_host.hpp"
 #include "summary_host.hpp"
 
@@ -48,6 +49,10 @@ hipError_t launch_scatter(const DevSim& S, const void* pairs, uint32_t n,
                           const raft_gather_layout_t& Y, const void* in, hipStream_t st);
 hipError_t launch_clone(const DevSim& T, const DevSim& Src, const void* pairs, uint32_t n,
                         uint64_t stride, hipStream_t st);
+hipError_t launch_restart(const DevSim& S, const void* pairs, uint32_t n, uint32_t mode, uint32_t T,
+                          hipStream_t st);
+hipError_t launch_restart_where(const DevSim& S, uint32_t fault_mask, uint32_t mode, uint32_t T,
+                                uint32_t* count, hipStream_t st);
 }  // namespace rs
 
 using rs::DevSim;
@@ -125,6 +130,10 @@ struct Shard {
   // source shard, the event the target shard's stream waits for before it reads this shard.
   hipEvent_t cev;
   double clone_ms;
+  // raft_restart_write / raft_restart_where (restart_kernel, restart_where_kernel,
+  // scatter_kernel.hip) upload their list, or keep their counter, in the same scratch and time
+  // their kernels with the same events (raftsim_diag_restart_ms).
+  double restart_ms;
 };
 
 // Exported functions take their C linkage from the declarations in include/raftsim.h.
@@ -1766,6 +1775,128 @@ int64_t raft_clone_write(raft_sim_t* dst, const uint32_t* targets, raft_sim_t* s
 // the maximum over shards, in ms.
 extern "C" int raftsim_diag_clone_ms(raft_sim_t* dst, double* ms) {
   return diag_ms(dst, ms, &Shard::clone_ms);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Node restarts (include/raftsim.h, "Node restarts"; SIM_SPEC §4a). Everything that can refuse a
+// call is checked on the host first (restart_host.hpp), so a refused call has touched no device.
+// Both forms go through the pack calls' path: the shard's gather scratch takes a chunk's list of
+// (cluster, mask) pairs (8 bytes a pair, GATHER_SCRATCH_BYTES at a time) or, for the `where` form,
+// the shard's counter; an event pair stands around each kernel; all shards run at once and every
+// started shard is waited for (pack_wait). The host's bookkeeping of a touched shard is a
+// scatter's without INV_LITE (launch_plan.hpp, ON_RESTART).
+static int restart_args_ok(const raft_sim* r, uint32_t mode) {
+  if (mode > RAFT_RESTART_DURABLE)
+    return fail(-EINVAL, "mode must be RAFT_RESTART_AMNESIA (0) or RAFT_RESTART_DURABLE (1)");
+  if (!r) return fail(-EINVAL, "null sim");
+  return 0;
+}
+static int restart_horizon(const raft_sim* r) {
+  if (!rs::restart_horizon_ok(r->tick, r->cfg.el_base, r->cfg.el_span))
+    return fail(-ERANGE, "tick + el_base + el_span would reach 2^32-1");
+  return 0;
+}
+
+int64_t raft_restart_write(raft_sim_t* r, const uint32_t* clusters, const uint16_t* nodes,
+                           uint32_t n, uint32_t mode) {
+  int rc = restart_args_ok(r, mode);
+  if (rc) return rc;
+  if (n && !clusters) return fail(-EINVAL, "null cluster list");
+  if (n && !nodes) return fail(-EINVAL, "null node mask list");
+  uint32_t at = 0;
+  char what[160];
+  switch (rs::restart_list_fault(clusters, nodes, n, r->cfg.n_clusters, r->cfg.nodes, &at)) {
+    case rs::RESTART_OK: break;
+    case rs::RESTART_OUTSIDE: return pack_cluster_ok(r, clusters, at);
+    case rs::RESTART_TWICE:
+      snprintf(what, sizeof what, "clusters[%u] = %u is named twice", at, clusters[at]);
+      return fail(-EINVAL, "%s", what);
+    case rs::RESTART_MASK:
+      snprintf(what, sizeof what, "nodes[%u] = 0x%x names no node or a node outside ids 1..%u", at,
+               nodes[at], r->cfg.nodes);
+      return fail(-EINVAL, "%s", what);
+  }
+  if ((rc = restart_horizon(r))) return rc;
+  if (r->poisoned) return unusable();
+  if (!n) return 0;
+
+  const size_t G = r->sh.size();
+  const rs::RestartPlan plan = rs::restart_plan(clusters, nodes, n, r->lo.data(), (uint32_t)G,
+                                                GATHER_SCRATCH_BYTES / sizeof(rs::RestartPair));
+  std::vector<size_t> first(G, 0), count(G, 0);          // per shard: its chunks of the plan
+  for (size_t i = 0; i < plan.chunks.size(); ++i) {
+    const uint32_t d = plan.chunks[i].shard;
+    if (!count[d]) first[d] = i;
+    ++count[d];
+  }
+  const uint32_t T = (uint32_t)r->tick;
+  PackCall hip = {"raft_restart_write"};
+  std::vector<size_t> started;
+  for (size_t d = 0; d < G && !hip.rc; ++d) {
+    if (!count[d]) continue;
+    Shard* s = r->sh[d];
+    started.push_back(d);
+    if (!hip.step(hipSetDevice(s->cfg.device))) break;
+    rs::invalidate(s->ls, rs::ON_RESTART);
+    size_t need = 0;
+    for (size_t i = first[d]; i < first[d] + count[d]; ++i)
+      need = std::max(need, plan.chunks[i].pairs * sizeof(rs::RestartPair));
+    if (!pack_scratch(hip, s, need) || !pack_events(hip, s, count[d])) break;
+    for (size_t i = 0; i < count[d] && !hip.rc; ++i) {
+      const rs::RestartChunk& ch = plan.chunks[first[d] + i];
+      hip.step(hipMemcpyAsync(s->gscratch, plan.pairs.data() + ch.pair0,
+                              ch.pairs * sizeof(rs::RestartPair), hipMemcpyHostToDevice,
+                              s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i], s->stream)) &&
+          hip.step(rs::launch_restart(s->d, s->gscratch, (uint32_t)ch.pairs, mode, T, s->stream)) &&
+          hip.step(hipEventRecord(s->gev[2 * i + 1], s->stream));
+    }
+  }
+  // every started shard is waited for, also after an error: its uploads read the plan
+  for (size_t d : started) pack_wait(hip, r->sh[d], count[d], &Shard::restart_ms);
+  if (!hip.rc)
+    for (size_t d = 0; d < G; ++d)
+      if (!count[d]) r->sh[d]->restart_ms = 0;
+  return hip.rc ? hip.rc : (int64_t)plan.nodes;
+}
+
+int64_t raft_restart_where(raft_sim_t* r, uint32_t fault_mask, uint32_t mode) {
+  if (fault_mask == 0 || fault_mask > 31) return fail(-EINVAL, "fault_mask must be 1..31");
+  int rc = restart_args_ok(r, mode);
+  if (rc) return rc;
+  if ((rc = restart_horizon(r))) return rc;
+  if (r->poisoned) return unusable();
+
+  const size_t G = r->sh.size();
+  const uint32_t T = (uint32_t)r->tick;
+  std::vector<uint32_t> found(G, 0);                     // the shards' counters, read back
+  PackCall hip = {"raft_restart_where"};
+  size_t started = 0;
+  for (size_t d = 0; d < G && !hip.rc; ++d) {
+    Shard* s = r->sh[d];
+    ++started;
+    if (!hip.step(hipSetDevice(s->cfg.device))) break;
+    rs::invalidate(s->ls, rs::ON_RESTART);
+    if (!pack_scratch(hip, s, sizeof(uint32_t)) || !pack_events(hip, s, 1)) break;
+    uint32_t* const dcount = reinterpret_cast<uint32_t*>(s->gscratch);
+    hip.step(hipMemsetAsync(dcount, 0, sizeof(uint32_t), s->stream)) &&
+        hip.step(hipEventRecord(s->gev[0], s->stream)) &&
+        hip.step(rs::launch_restart_where(s->d, fault_mask, mode, T, dcount, s->stream)) &&
+        hip.step(hipEventRecord(s->gev[1], s->stream)) &&
+        hip.step(d2h(s, &found[d], dcount, 1));
+  }
+  // every started shard is waited for, also after an error: its copy writes `found`
+  for (size_t d = 0; d < started; ++d) pack_wait(hip, r->sh[d], 1, &Shard::restart_ms);
+  int64_t total = 0;
+  for (uint32_t f : found) total += f;
+  return hip.rc ? hip.rc : total;
+}
+
+// Diagnostic (not part of include/raftsim.h): device time of the last raft_restart_write's or
+// raft_restart_where's kernels (HIP events around each kernel on each shard's stream, summed), the
+// maximum over shards, in ms.
+extern "C" int raftsim_diag_restart_ms(raft_sim_t* r, double* ms) {
+  return diag_ms(r, ms, &Shard::restart_ms);
 }
 
 // Build identity (not part of include/raftsim.h): the hash of the kernel sources this library was

@@ -269,4 +269,102 @@ hipError_t launch_clone(const DevSim& T, const DevSim& Src, const void* pairs, u
   return hipGetLastError();
 }
 
+// Node restarts (include/raftsim.h, "Node restarts"; SIM_SPEC §4a): the unit's third state writer.
+// A restart writes hot words only -- no queue slot, arena slot or stream slot moves -- so both
+// kernels take the tick kernel's mapping instead of the packs': one lane per node, floor(64 / N)
+// whole clusters per wave, and a store of field f is one run of N adjacent words per cluster (word
+// HOT_CW + f * N + k), of which the lanes of the restarted nodes take part. Every word is
+// hot_restart's (node_codec.hpp) of the node's words before it: a lane reads and writes its own
+// node's words alone, field after field, and the one word it reads after writing another (the
+// frontier, for the base) is one a restart keeps. The cluster's first lane zeroes words 5-7 (the
+// unused word and the steady certificate, as scatter and clone leave them) of a cluster with a
+// restarted node; words 0-4 (hwm, client cursor) stay.
+__device__ __forceinline__ void restart_lane(const DevSim& S, uint32_t c, uint32_t k, bool node,
+                                             bool head, uint32_t mode, uint32_t T) {
+  const uint32_t N = S.N;
+  if (node) {
+    const DrawKeys dk = {S.el_base, S.el_span, S.key0, S.key1};
+    uint32_t* const h = hot_node(S, c, k);
+    const uint32_t F = hot_fields(N);
+    for (uint32_t f = 0; f < F; ++f) h[f * N] = hot_restart(h, N, f, mode, T, S.goff + c, k, dk);
+  }
+  if (head) {
+    uint32_t* const cl = hot_cl(S, c);
+    cl[CL_CLIENT_COUNT + 1] = 0;
+    cl[CL_CTERM] = 0;
+    cl[CL_CERT] = 0;
+  }
+}
+
+constexpr uint32_t RESTART_WAVES = PACK_BLOCK / 64;
+
+// restart_kernel — the list form: node id j of cluster pairs[r].x of shard S is restarted where bit
+// j of pairs[r].y is set. The waves stride over the list, floor(64 / N) pairs at a time.
+__global__ void __launch_bounds__(PACK_BLOCK)
+restart_kernel(const DevSim S, const uint2* __restrict__ pairs, uint32_t n, uint32_t mode,
+               uint32_t T) {
+  const uint32_t N = S.N, CPW = 64 / N, lane = threadIdx.x & 63;
+  const uint32_t slot = lane / N, k = lane - slot * N;
+  const uint32_t wave = blockIdx.x * RESTART_WAVES + (threadIdx.x >> 6);
+  const uint32_t waves = gridDim.x * RESTART_WAVES;
+  if (slot >= CPW) return;                               // the wave's spare lanes
+  for (uint64_t r = (uint64_t)wave * CPW + slot; r < n; r += (uint64_t)waves * CPW) {
+    const uint2 p = pairs[r];
+    if (p.x >= S.C) continue;                            // (the host refuses such a list)
+    const uint32_t ids = p.y & ((2u << N) - 2);          // (... and a bit outside ids 1..N)
+    restart_lane(S, p.x, k, (ids >> (k + 1)) & 1, k == 0 && ids, mode, T);
+  }
+}
+
+// restart_where_kernel — the supervisor form: one pass over the hot blocks of shard S restarts every
+// node whose fault code f has bit f set in fault_mask (bit 0: the running nodes). A wave reads the
+// flags words of its clusters, a word per lane; only clusters with a matching node are written. The
+// matches are counted per wave (the popcount of the ballot, a scalar) and added once per wave into
+// the shard's counter *count, which the host zeroes before the launch and reads once after it.
+__global__ void __launch_bounds__(PACK_BLOCK)
+restart_where_kernel(const DevSim S, uint32_t fault_mask, uint32_t mode, uint32_t T,
+                     uint32_t* __restrict__ count) {
+  const uint32_t N = S.N, CPW = 64 / N, lane = threadIdx.x & 63;
+  const uint32_t slot = lane / N, k = lane - slot * N, seg = (1u << N) - 1;
+  const uint32_t wave = blockIdx.x * RESTART_WAVES + (threadIdx.x >> 6);
+  const uint32_t waves = gridDim.x * RESTART_WAVES;
+  const uint32_t groups = (S.C + CPW - 1) / CPW;         // C * N < 2^31: no overflow
+  uint32_t total = 0;                                    // wave-uniform
+  for (uint32_t g = wave; g < groups; g += waves) {
+    const uint32_t c = g * CPW + slot;
+    const bool act = slot < CPW && c < S.C;
+    bool hit = false;
+    if (act) hit = (fault_mask >> fl_fault(hot_node(S, c, k)[HF_FLAGS * N])) & 1;
+    const uint64_t b = __ballot(hit);
+    total += (uint32_t)__popcll(b);
+    // slot * N <= 63, also on the wave's spare lanes
+    restart_lane(S, c, k, hit, act && k == 0 && ((uint32_t)(b >> (slot * N)) & seg), mode, T);
+  }
+  if (lane == 0 && total) atomicAdd(count, total);
+}
+
+inline dim3 restart_grid(uint32_t clusters, uint32_t N) {
+  const uint32_t CPW = 64 / N, waves = (clusters + CPW - 1) / CPW;
+  return dim3(std::min((waves + RESTART_WAVES - 1) / RESTART_WAVES, PACK_MAX_GRID));
+}
+
+// Restart the nodes pairs[i].y (bit j: id j) of cluster pairs[i].x of S (device list, shard-local
+// ids), n pairs, at tick T in mode `mode` (raft_restart_mode).
+hipError_t launch_restart(const DevSim& S, const void* pairs, uint32_t n, uint32_t mode, uint32_t T,
+                          hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(restart_kernel, restart_grid(n, S.N), dim3(PACK_BLOCK), 0, st, S,
+                     static_cast<const uint2*>(pairs), n, mode, T);
+  return hipGetLastError();
+}
+
+// Restart every node of S whose fault code is in fault_mask; *count (device, zeroed by the caller
+// on the same stream) receives their number.
+hipError_t launch_restart_where(const DevSim& S, uint32_t fault_mask, uint32_t mode, uint32_t T,
+                                uint32_t* count, hipStream_t st) {
+  hipLaunchKernelGGL(restart_where_kernel, restart_grid(S.C, S.N), dim3(PACK_BLOCK), 0, st, S,
+                     fault_mask, mode, T, count);
+  return hipGetLastError();
+}
+
 }  // namespace rs

@@ -15,7 +15,10 @@ from . import _build
 from ._abi import COUNTER_NAMES  # noqa: F401
 from . import _abi
 from ._backend import (FAULT_NAMES, ROLE_NAMES, Backend, ClusterPack, GpuBackend,  # noqa: F401
-                       RaftSimError, check_clone_fits, check_pack_fits, replay_config)
+                       RaftSimError, check_clone_fits, check_pack_fits, replay_config,
+                       restart_lists, restart_mode)
+from .restart import (philox, restart_by_writes, restart_deadline, restart_record,  # noqa: F401
+                      supervise)
 
 PKG_DIR = Path(__file__).resolve().parent.parent          # raft-simulation_amd/
 LIB_PATH = Path(os.environ.get("RAFTSIM_LIB", PKG_DIR / "build" / "libraftsim.so"))

@@ -327,6 +327,18 @@ CLONE_SYMBOLS = ["raft_clone_" + n for n in _CLONE_SIGS]
 CLONE_SHAPE = ("nodes", "inbox_cap", "log_cap", "arena_cap", "commit_stream_cap")
 
 
+# Node restarts (include/raftsim.h, "Node restarts"): the list form (sim, clusters, node masks, n,
+# mode) and the supervisor form (sim, fault_mask, mode); both return the nodes restarted.
+_RESTART_SIGS = {
+    "write": (C.c_int64, [C.c_void_p, P(C.c_uint32), P(C.c_uint16), C.c_uint32, C.c_uint32]),
+    "where": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32]),
+}
+RESTART_SYMBOLS = ["raft_restart_" + n for n in _RESTART_SIGS]
+RESTART_MODES = {"amnesia": 0, "durable": 1}                  # raft_restart_mode
+# raft_node_t.fault by name: bit f of a raft_restart_where fault_mask is fault code f
+FAULT_CODES = {"running": 0, "ioobe": 1, "npe": 2, "cce": 3, "overflow": 4}
+
+
 def bind(lib, prefix, optional=(), sigs=None):
     """Attach argtypes/restype to `lib`'s `prefix + name` functions; return {name: fn}."""
     fns = {}

@@ -453,6 +453,7 @@ class GpuBackend(Backend):
         self._gather = _abi.bind(self._lib, "raft_gather_", sigs=_abi._GATHER_SIGS)
         self._scatter = _abi.bind(self._lib, "raft_scatter_", sigs=_abi._SCATTER_SIGS)
         self._clone = _abi.bind(self._lib, "raft_clone_", sigs=_abi._CLONE_SIGS)
+        self._restart = _abi.bind(self._lib, "raft_restart_", sigs=_abi._RESTART_SIGS)
 
     # -- what the three device-side queries share ------------------------------------------------
     @staticmethod
@@ -760,12 +761,94 @@ class GpuBackend(Backend):
         handle."""
         return self._diag_ms("raftsim_diag_clone_ms")
 
+    # -- node restarts (include/raftsim.h, "Node restarts") --------------------------------------
+    def restart(self, targets, nodes=None, mode="amnesia"):
+        """Start halted (or any) nodes again on the device at the handle's tick
+        (raft_restart_write; SIM_SPEC §4a): returns the number of nodes restarted. `targets` are
+        handle-local cluster ids, in any order, none twice, each paired with nodes[i]: a mask (bit
+        j = node id j, as `votes`) or a list of node ids; or the record dicts select() returns,
+        for which `nodes` defaults to the record's `halted` ids, so
+        sim.restart(sim.select(any=["halted"])[1]) restarts every halted node. mode "amnesia" is
+        the reference's JVM started again (init-node, a fresh log, nothing read from disk),
+        "durable" keeps current_term, voted_for and the log (Raft's Figure 2). Both empty the
+        node's queues and re-arm its election timer from the current tick. ValueError names the
+        position of a bad shape. All or nothing: a refused call (RaftSimError naming the first
+        offending position) restarted nothing."""
+        cl, masks = restart_lists(targets, nodes, self.C, self.N)
+        self.host_written = True
+        return self._check(int(self._restart["write"](
+            self._h, cl.ctypes.data_as(C.POINTER(C.c_uint32)),
+            masks.ctypes.data_as(C.POINTER(C.c_uint16)), cl.size, restart_mode(mode))))
+
+    def restart_where(self, faults=("ioobe", "npe", "cce", "overflow"), mode="amnesia"):
+        """Restart every node of the handle whose fault is one of `faults` (names of
+        _abi.FAULT_CODES; "running" names the nodes that have not halted), found and counted on
+        the device in one pass (raft_restart_where): returns the number of nodes restarted."""
+        mask = self._mask(faults, {k: 1 << v for k, v in _abi.FAULT_CODES.items()}, "fault")
+        self.host_written = True
+        return self._check(int(self._restart["where"](self._h, mask, restart_mode(mode))))
+
+    def last_restart_ms(self):
+        """Diagnostic: device time (HIP events) of the last restart()'s or restart_where()'s
+        kernels."""
+        return self._diag_ms("raftsim_diag_restart_ms")
+
     def replay_config(self, cluster, **overrides):
         """The config (a dict of raft_sim_config_t fields) of a handle that simulates cluster
         `cluster` of this one alone: Philox is keyed by the global cluster id, so n_clusters=1 at
         cluster_offset + cluster reproduces it exactly from init-node. The trace rings are on by
         default (the `wait` trace, F3); `overrides` replace any field."""
         return replay_config(self.config, cluster, **overrides)
+
+
+def restart_mode(mode):
+    """raft_restart_mode of a name of _abi.RESTART_MODES or of 0 / 1."""
+    if mode in _abi.RESTART_MODES:
+        return _abi.RESTART_MODES[mode]
+    if mode in (0, 1):
+        return int(mode)
+    raise ValueError(f"unknown restart mode {mode!r} (one of {list(_abi.RESTART_MODES)})")
+
+
+def restart_lists(targets, nodes, n_clusters, n_nodes):
+    """The (clusters, masks) arrays of GpuBackend.restart (needs no library). ValueError names the
+    position of a cluster outside the handle, a cluster named twice, a missing or empty node list
+    and a node id outside 1..n_nodes."""
+    targets = list(targets)
+    if nodes is not None:
+        nodes = list(nodes)
+        if len(nodes) != len(targets):
+            raise ValueError(f"restart: {len(nodes)} node masks for {len(targets)} targets")
+    ids_mask = ((1 << (n_nodes + 1)) - 1) & ~1
+    cl = np.zeros(len(targets), dtype=np.uint32)
+    masks = np.zeros(len(targets), dtype=np.uint16)
+    seen = set()
+    for i, t in enumerate(targets):
+        c = int(t["cluster"] if isinstance(t, dict) else t)
+        if not 0 <= c < n_clusters:
+            raise ValueError(f"restart: targets[{i}] = {c} is outside the handle's {n_clusters}")
+        if c in seen:
+            raise ValueError(f"restart: targets[{i}] = {c} is named twice")
+        seen.add(c)
+        if nodes is not None:
+            m = nodes[i]
+        elif isinstance(t, dict) and "halted" in t:
+            m = t["halted"]
+        else:
+            raise ValueError(f"restart: targets[{i}] = {c} has no node mask (give `nodes`, or "
+                             "select() records, whose halted nodes are taken)")
+        if not isinstance(m, (int, np.integer)):
+            ids = [int(j) for j in m]
+            bad = [j for j in ids if not 1 <= j <= n_nodes]
+            if bad:
+                raise ValueError(f"restart: nodes[{i}] names node id {bad[0]} outside 1..{n_nodes}")
+            m = sum(1 << j for j in set(ids))
+        m = int(m)
+        if m == 0 or m & ~ids_mask:
+            raise ValueError(f"restart: nodes[{i}] = {m:#x} names no node or a node outside "
+                             f"ids 1..{n_nodes}")
+        cl[i], masks[i] = c, m
+    return cl, masks
 
 
 def check_pack_fits(config, pack, who):

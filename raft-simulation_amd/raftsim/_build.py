@@ -28,6 +28,7 @@ KERNEL_SOURCES = ["raft-simulation_amd/csrc/tick_kernel.hip",
                   "raft-simulation_amd/csrc/scatter_kernel.hip",
                   "raft-simulation_amd/csrc/scatter_host.hpp",
                   "raft-simulation_amd/csrc/clone_host.hpp",
+                  "raft-simulation_amd/csrc/restart_host.hpp",
                   "raft-simulation_amd/csrc/launch_plan.hpp",
                   "raft-simulation_amd/csrc/node_codec.hpp",
                   "raft-simulation_amd/csrc/pack.hpp",

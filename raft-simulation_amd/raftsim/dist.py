@@ -106,6 +106,17 @@ def reduce_sum(x: float, device=None) -> float:
     return float(t.item())
 
 
+def reduce_restarts(n: int, device=None) -> int:
+    """All-reduce (SUM) the count a rank's restart() or restart_where() returned over the default
+    process group: the nodes restarted in the whole job."""
+    import torch
+    import torch.distributed as dist
+
+    t = torch.tensor([int(n)], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return int(t.item())
+
+
 def reduce_min(x: int, device=None) -> int:
     import torch
     import torch.distributed as dist

@@ -38,7 +38,7 @@ PRETTY = [
     (r"11tick_kernelILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)", lambda m:
      f"tick_kernel<N={m[1]}, TRACE={m[2]}, SPEC={m[3]}, LITE={m[4]}{', STORM' * (m[5] == '1')}>"),
     (r"\d+((?:steady|storm)_lane_kernel)ILi(\d)E", lambda m: f"{m[1]}<N={m[2]}>"),
-    (r"\d+((?:census|viol|audit|gather|scatter|clone)_\w*?kernel)E", lambda m: m[1]),
+    (r"\d+((?:census|viol|audit|gather|scatter|clone|restart)_\w*?kernel)E", lambda m: m[1]),
     (r"19summary_fold_kernelI\d+raft_([a-z]+)E", lambda m: f"summary_fold_kernel<{m[1]}>"),
     (r"12audit_kernelILj(\d)ELj(\d+)E", lambda m: f"audit_kernel<N={m[1]}, G={m[2]}>"),
     # the compaction (compact.hpp): compact_count<viol>; the scan, one copy per file that uses it
