@@ -409,7 +409,7 @@ __device__ __forceinline__ void rounds(St& s, uint32_t th, uint32_t tend, uint32
     s.nae += F * K;
     s.nar += F * K;
   }
-  if (tk < tend) {                                // the round the launch's end cuts
+  if (__builtin_expect(tk < tend, 0)) {           // the round the launch's end cuts (rare)
     s.Ltr = trace_event(s.Ltr, tk, 7, 0, 0, RAFT_LEADER, T, 0);
     ++s.nhb;
     s.Ldl = tk + hb;
@@ -429,15 +429,19 @@ __device__ __forceinline__ void run_launch(St& s, uint32_t mid, uint32_t th0, ui
                                            uint32_t d, uint32_t hb, uint32_t el_base, uint32_t P,
                                            const BandSets& bs, const LaunchBand& lb) {
   bool whole = true;                              // the round in progress finished in this launch
-  if (mid == 1) {
-    if (th0 + d < tend) s.append_entries(th0 + d, d, el_base);
-    else whole = false;
+  // (Rare, and tested once for the lanes here: a wave none of whose clusters is in a round at t0
+  // branches once, to no block of this, and the common stream falls through.)
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(mid != 0) != 0, 0)) {
+    if (mid == 1) {
+      if (th0 + d < tend) s.append_entries(th0 + d, d, el_base);
+      else whole = false;
+    }
+    if (mid && whole) {
+      s.responses(th0, tend, d, hb);
+      whole = !s.queued();
+    }
   }
-  if (mid && whole) {
-    s.responses(th0, tend, d, hb);
-    whole = !s.queued();
-  }
-  if (whole) rounds(s, mid ? th0 + P : th0, tend, d, hb, el_base, bs, lb);
+  if (__builtin_expect(whole, 1)) rounds(s, mid ? th0 + P : th0, tend, d, hb, el_base, bs, lb);
 }
 
 // Which round of the period-P schedule is in progress at t0, from the leader's deadline Ldl and
@@ -473,6 +477,83 @@ __device__ __forceinline__ Schedule schedule(uint32_t t0, uint32_t tend, uint32_
   }
   s.nxt = min((s.mid == 2 ? s.th0 + P : s.th0) + d, tend);
   return s;
+}
+
+// The tail every path of the kernel ends with, one copy of each piece: the line-0 wave runs them
+// where its body ends and returns, the other paths where they join.
+//
+// Dirty lines back to memory whole (dl: bit ln set in the lanes whose cluster's line ln changed,
+// ln < LINES): a wave instruction writes eight clusters' line (8 lanes x 16 B each), read from the
+// image (line ln of cluster cc is its chunks 8 ln .. 8 ln + 7): the eight reads of a line first,
+// then the stores. The stores write through to memory (sc1: the lines leave the XCD's L2 as the
+// waves end, not at the launch's end; the next launch reads them from the Infinity Cache either
+// way). They are not in the compiler's wait counts: the catch-up waits for them itself.
+template <int N, int LINES>
+__device__ __forceinline__ void store_lines(const DevSim& S, char* img, uint32_t cbase,
+                                            uint32_t lane, uint32_t dl) {
+  constexpr uint32_t HB = hot_block_words(N);
+  // The lane's address terms are computed here, at each call: the lane id passes through an empty
+  // statement. Shared between the two calls they are computed at the kernel's top and stay live
+  // across every other path, which cost the N = 2 and N = 3 kernels a wave of occupancy each.
+  asm volatile("" : "+v"(lane));
+  uint32_t* const wbase = S.hot + (size_t)cbase * HB;      // the wave's first block
+  const uint32_t sub = lane >> 3, q8 = lane & 7;
+#pragma unroll
+  for (int ln = 0; ln < LINES; ++ln) {
+    const uint64_t bal = __builtin_amdgcn_ballot_w64((dl >> ln) & 1);
+    if (!bal) continue;                                  // wave-uniform
+    uint4 xs[8];
+#pragma unroll
+    for (int gq = 0; gq < 8; ++gq)
+      xs[gq] = *lds_at<const uint4>(img, img_off(8 * gq + sub, 8 * ln + q8));
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    if (__builtin_expect(bal == ~0ull, 1)) {
+      // every cluster of a full wave (the headline's every wave): eight stores with no
+      // predicate, a lane's address in the first group of eight blocks once and one 64-bit add
+      // per further group. (Addresses stay in vector registers: a store in an asm statement
+      // that took its base from scalar registers would stand outside the compiler's hazard
+      // checks, and a scalar register a vector instruction wrote needs five wait states
+      // before a memory instruction reads it.)
+      uint32_t* const dst0 = wbase + sub * HB + 4 * (8 * ln + q8);
+#pragma unroll
+      for (int gq = 0; gq < 8; ++gq) {
+        const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
+        uint32_t* const dst = dst0 + (size_t)(8 * gq) * HB;
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
+      }
+      continue;
+    }
+#pragma unroll
+    for (int gq = 0; gq < 8; ++gq) {
+      const uint32_t cc = 8 * gq + sub;
+      if ((bal >> cc) & 1) {
+        const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
+        uint32_t* const dst = wbase + cc * HB + 4 * (8 * ln + q8);
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
+      }
+    }
+  }
+}
+
+// wave wid's copy of the counter block
+__device__ __forceinline__ unsigned long long* wave_counters(const DevSim& S, uint32_t wid) {
+  return S.ctr + (size_t)(wid % CTR_COPIES) * CTR_STRIDE;
+}
+// Counters: heartbeats, append-entries, append-responses; every message is delivered. One
+// wave-wide sum each, added by five lanes to the wave's copy of the counter block.
+template <int N>
+__device__ __forceinline__ void add_counters(const DevSim& S, uint32_t lane, uint32_t wid,
+                                             uint32_t nhb, uint32_t nae, uint32_t nar) {
+  const uint32_t h = wave_sum(nhb), a = wave_sum(nae), r = wave_sum(nar);
+  // lane 0 .. 4: heartbeats, append-entries, append-responses, sent, delivered. The index is
+  // a nibble of a constant and the value a chain of selects: one branch, around the atomic.
+  constexpr uint32_t IDX = RAFT_CTR_EV_HEARTBEAT | RAFT_CTR_EV_AE << 4 | RAFT_CTR_EV_AR << 8 |
+                           RAFT_CTR_SENT << 12 | RAFT_CTR_DELIVERED << 16;
+  static_assert(RAFT_CTR_DELIVERED < 16, "a nibble per index");
+  const uint32_t msgs = (uint32_t)(N - 1) * h + a;
+  const uint32_t idx = (IDX >> (4 * (lane & 7))) & 15u;
+  const uint32_t v = msel(lane == 0, h, msel(lane == 1, a, msel(lane == 2, r, msgs)));
+  if (lane < 5 && v) atomicAdd(&wave_counters(S, wid)[idx], (unsigned long long)v);
 }
 
 
@@ -620,7 +701,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
                      (uint32_t)__builtin_amdgcn_readlane(park, 1),
                      (uint32_t)__builtin_amdgcn_readlane(park, 2)};
   };
-  if (reporter && prev_bails) {
+  if (__builtin_expect(reporter && prev_bails, 0)) {
     if (S.bail_report) *S.bail_report = prev_bails;
     *S.nbail_zero = 0;
   }
@@ -632,10 +713,39 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   bool el = false;                             // the cluster's election ran here (general path)
   uint32_t el_to = 0;                          // its timeouts (two candidates: a tie)
 #ifdef RS_WAVELOG
-  uint64_t wl_x1 = 0, wl_x2 = 0, wl_x3 = 0, wl_lend = 0;
+  uint64_t wl_x1 = 0, wl_x2 = 0, wl_x3 = 0, wl_lend = 0, wl_sb = 0;
   uint32_t wl_cut = 0;
   asm volatile("" ::"v"(w[CL_CERT]), "v"(w[HOT_CW]));
   wl_loop = wall_clock64();                   // line 0 loaded
+  // the wave's record, behind its line stores (wl_sb: stamped before their first image read)
+  auto wave_record = [&]() __attribute__((always_inline)) {
+    const uint64_t wl_end = wall_clock64();
+    const uint32_t wl_events = nhb + nae + nar;
+    const uint32_t emax = ~wave_min(~wl_events), emin = wave_min(wl_events);
+    if (lane == 0 && S.wavelog) {
+      uint32_t hw, xcc;
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+      uint4* rec = reinterpret_cast<uint4*>(S.wavelog + (size_t)(blockIdx.x * 4 + wave) * 32);
+      rec[0] = make_uint4((uint32_t)wl_start, (uint32_t)(wl_start >> 32), (uint32_t)wl_end,
+                          (uint32_t)(wl_end >> 32));
+      rec[1] = make_uint4(wl_trips, hw, xcc, wl_first);
+      rec[2] = make_uint4((uint32_t)(wl_loop - wl_start), (uint32_t)(wl_lend - wl_start), emin, emax);
+      rec[3] = make_uint4(wl_ph[0], wl_ph[1], wl_ph[2], wl_ph[3]);
+      rec[4] = make_uint4(wl_ph[4], 0, 0, (uint32_t)(wl_sb - wl_start));
+      rec[5] = make_uint4((uint32_t)(wl_x1 - wl_start), (uint32_t)(wl_x2 - wl_start),
+                          (uint32_t)(wl_x3 - wl_start), wl_cut);
+    }
+  };
+  // the wave's end: its stores issued, counted, its catch-up run
+  auto wave_done = [&]() __attribute__((always_inline)) {
+    if (lane == 0 && S.wavelog) {
+      const uint64_t wl_done = wall_clock64();
+      uint32_t* rec = S.wavelog + (size_t)(blockIdx.x * 4 + wave) * 32;
+      rec[17] = (uint32_t)wl_done;
+      rec[18] = (uint32_t)(wl_done >> 32);
+    }
+  };
 #endif
 
   // ------------------------------------------- the certified path from line 0 alone
@@ -710,15 +820,17 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     strong = strong & (msel(lmid != 0, lth0 + P, lth0) - t0 < P);
   }
   const bool line0_wave = !__builtin_amdgcn_ballot_w64(active && !strong);   // uniform
-  if (line0_wave) {
+  if (__builtin_expect(line0_wave, 1)) {
     // ----------------------------------------- the line-0 body: the whole launch in node order
     // (It stands right behind the decision: its state is dead before the other paths load their
     // lines. Behind them it stayed live across them and cost the N = 2 kernel a wave of occupancy.)
+    // The wave ends here, where its body ends: its line stores, its counters and its return stand
+    // in the instruction stream right behind the body, not behind the other paths' code.
 #ifdef RS_WAVELOG
     asm volatile("" ::"v"(no.Ltr), "v"(no.Ldl), "v"(no.tr[0]), "v"(lth0));
     wl_x1 = wl_x2 = wall_clock64();           // fields extracted, the path decided
 #endif
-    if (active) {
+    if (__builtin_expect(active, 1)) {
       const LaunchBand lb{t0, parked_band()};
       run_launch(no, lmid, lth0, tend, d, hb, el_base, P, bs, lb);
       nhb = no.nhb; nae = no.nae; nar = no.nar;
@@ -759,14 +871,14 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
       for (int i = (int)HOT_CW / 4; i < (CH_END < 8 ? CH_END : 8); ++i)
         *lds_at<uint4>(img, img_off(lane, i)) = chunk(i);
       dl = (nhb | nae | nar) != 0;
-      if (CH_END > 8 && (lmid || no.qin || no.rc)) {   // rare
+      if (CH_END > 8 && __builtin_expect(lmid || no.qin || no.rc, 0)) {   // rare
         uint4* const bp = reinterpret_cast<uint4*>(S.hot + (size_t)c * HB);
 #pragma unroll
         for (int i = 8; i < CH_END; ++i) bp[i] = chunk(i);
       }
     }
     // messages in flight at the launch's end back to the rings, heads at slot 0 (rare)
-    if (__builtin_amdgcn_ballot_w64(active && (no.qin || no.rc))) {   // wave-uniform
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(active && (no.qin || no.rc)) != 0, 0)) {   // wave-uniform
       if (active && no.qin) {
 #pragma unroll
         for (int k = 0; k < N; ++k) {
@@ -793,7 +905,20 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     wl_lend = wall_clock64();                   // the image and the rings written
     // some cluster of the wave had a round in progress at the launch's start or at its end
     wl_cut = __builtin_amdgcn_ballot_w64(active && (lmid || no.qin || no.rc)) ? 1u : 0u;
+    wl_sb = wall_clock64();
 #endif
+    // Only line 0 can be dirty here. The wave bailed no cluster (run_launch records none) and ran
+    // no election (el is the general path's): no catch-up, no election counters. The kernel has
+    // no workgroup barrier, so the wave's siblings run on without it.
+    store_lines<N, 1>(S, img, cbase, lane, dl);
+#ifdef RS_WAVELOG
+    wave_record();
+#endif
+    add_counters<N>(S, lane, blockIdx.x * 4 + wave, nhb, nae, nar);
+#ifdef RS_WAVELOG
+    wave_done();
+#endif
+    return;
   }
 
   // The steady certificate (device.hpp): a cluster the last steady launch left at its fixed point
@@ -801,7 +926,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   // lacks one; otherwise those words read as the fixed point's (zero).
   uint32_t Lc = 0;
   bool cert = false, full = false;
-  if (!line0_wave) {
+  {
     load_line(1, true);
 #pragma unroll
     for (int i = 32; i < NW4 * 4; ++i) w[i] = 0;
@@ -836,7 +961,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
   FixedPoint<N> fx;                           // (set below, by the waves that use it)
   const LaunchBand no_band{t0, fpa::Band{0, 0, 0}};   // (FixedPoint's rounds() reads none of it)
   bool lean = false;
-  if (!line0_wave) {
+  {
     lean = vouched && cfg_ok;
     const uint32_t L = Lc;
     fx.L = L; fx.Lid = L + 1; fx.Lterm = lword(HF_TERM, L); fx.Lcommit = 0;
@@ -882,7 +1007,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #pragma unroll
     for (int j = 0; j < F; ++j) lean = lean && fx.fdl[j] >= sc.nxt;
   }
-  const bool lean_wave = !line0_wave && !__builtin_amdgcn_ballot_w64(active && !lean);   // uniform
+  const bool lean_wave = !__builtin_amdgcn_ballot_w64(active && !lean);   // uniform
   bool wb = false;
   if (lean_wave) {
 #ifdef RS_WAVELOG
@@ -923,7 +1048,7 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
 #ifdef RS_WAVELOG
     wl_lend = wall_clock64();                   // the image and the rings written
 #endif
-  } else if (!line0_wave) {
+  } else {
 #ifdef RS_WAVELOG
     wl_loop = wall_clock64();
 #endif
@@ -1690,103 +1815,29 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     fx.to_rings(S, c, wb);
     nhb = fx.nhb; nae = fx.nae; nar = fx.nar;
   }   // the general path
-  // Dirty lines back to memory whole: a wave instruction writes eight clusters' line (8 lanes x
-  // 16 B each), read from the image (line ln of cluster cc is its chunks 8 ln .. 8 ln + 7): the
-  // eight reads of a line first, then the stores. The stores write through to memory (sc1: the
-  // lines leave the XCD's L2 as the waves end, not at the launch's end; the next launch reads them
-  // from the Infinity Cache either way). They are not in the compiler's wait counts: the catch-up
-  // below waits for them itself.
-  {
-    uint32_t* const wbase = S.hot + (size_t)cbase * HB;      // the wave's first block
-    const uint32_t sub = lane >> 3, q8 = lane & 7;
-#pragma unroll
-    for (int ln = 0; ln < IMGC / 8; ++ln) {
-      const uint64_t bal = __builtin_amdgcn_ballot_w64((dl >> ln) & 1);
-      if (!bal) continue;                                  // wave-uniform
-      uint4 xs[8];
-#pragma unroll
-      for (int gq = 0; gq < 8; ++gq)
-        xs[gq] = *lds_at<const uint4>(img, img_off(8 * gq + sub, 8 * ln + q8));
-      typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-      if (bal == ~0ull) {
-        // every cluster of a full wave (the headline's every wave): eight stores with no
-        // predicate, a lane's address in the first group of eight blocks once and one 64-bit add
-        // per further group. (Addresses stay in vector registers: a store in an asm statement
-        // that took its base from scalar registers would stand outside the compiler's hazard
-        // checks, and a scalar register a vector instruction wrote needs five wait states
-        // before a memory instruction reads it.)
-        uint32_t* const dst0 = wbase + sub * HB + 4 * (8 * ln + q8);
-#pragma unroll
-        for (int gq = 0; gq < 8; ++gq) {
-          const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
-          uint32_t* const dst = dst0 + (size_t)(8 * gq) * HB;
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
-        }
-        continue;
-      }
-#pragma unroll
-      for (int gq = 0; gq < 8; ++gq) {
-        const uint32_t cc = 8 * gq + sub;
-        if ((bal >> cc) & 1) {
-          const v4u xv = {xs[gq].x, xs[gq].y, xs[gq].z, xs[gq].w};
-          uint32_t* const dst = wbase + cc * HB + 4 * (8 * ln + q8);
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(xv) : "memory");
-        }
-      }
-    }
-  }
+  // The tail (store_lines, add_counters above): every line of the image may be dirty here.
 #ifdef RS_WAVELOG
-  {
-    const uint64_t wl_end = wall_clock64();
-    const uint32_t wl_events = nhb + nae + nar;
-    const uint32_t emax = ~wave_min(~wl_events), emin = wave_min(wl_events);
-    if (lane == 0 && S.wavelog) {
-      uint32_t hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      uint4* rec = reinterpret_cast<uint4*>(S.wavelog + (size_t)(blockIdx.x * 4 + wave) * 32);
-      rec[0] = make_uint4((uint32_t)wl_start, (uint32_t)(wl_start >> 32), (uint32_t)wl_end,
-                          (uint32_t)(wl_end >> 32));
-      rec[1] = make_uint4(wl_trips, hw, xcc, wl_first);
-      rec[2] = make_uint4((uint32_t)(wl_loop - wl_start), (uint32_t)(wl_lend - wl_start), emin, emax);
-      rec[3] = make_uint4(wl_ph[0], wl_ph[1], wl_ph[2], wl_ph[3]);
-      rec[4] = make_uint4(wl_ph[4], 0, 0, 0);
-      rec[5] = make_uint4((uint32_t)(wl_x1 - wl_start), (uint32_t)(wl_x2 - wl_start),
-                          (uint32_t)(wl_x3 - wl_start), wl_cut);
-    }
-  }
+  wl_sb = wall_clock64();
 #endif
-  // counters: heartbeats, append-entries, append-responses; every message is delivered. One
-  // wave-wide sum each, added by five lanes to the wave's copy of the counter block.
+  store_lines<N, IMGC / 8>(S, img, cbase, lane, dl);
+#ifdef RS_WAVELOG
+  wave_record();
+#endif
+  add_counters<N>(S, lane, blockIdx.x * 4 + wave, nhb, nae, nar);
   // Elections run here add a timeout, F request-votes and F vote responses, a leader, and the
-  // request-vote, vote-response and append-entries messages (3F; the responses are in a).
-  {
-    const uint32_t h = wave_sum(nhb), a = wave_sum(nae), r = wave_sum(nar);
-    unsigned long long* const ctr =
-        S.ctr + (size_t)((blockIdx.x * 4 + wave) % CTR_COPIES) * CTR_STRIDE;
-    {
-      // lane 0 .. 4: heartbeats, append-entries, append-responses, sent, delivered. The index is
-      // a nibble of a constant and the value a chain of selects: one branch, around the atomic.
-      constexpr uint32_t IDX = RAFT_CTR_EV_HEARTBEAT | RAFT_CTR_EV_AE << 4 | RAFT_CTR_EV_AR << 8 |
-                               RAFT_CTR_SENT << 12 | RAFT_CTR_DELIVERED << 16;
-      static_assert(RAFT_CTR_DELIVERED < 16, "a nibble per index");
-      const uint32_t msgs = (uint32_t)F * h + a;
-      const uint32_t idx = (IDX >> (4 * (lane & 7))) & 15u;
-      const uint32_t v = msel(lane == 0, h, msel(lane == 1, a, msel(lane == 2, r, msgs)));
-      if (lane < 5 && v) atomicAdd(&ctr[idx], (unsigned long long)v);
-    }
-    if (__builtin_amdgcn_ballot_w64(el)) {                   // wave-uniform
-      // per election: el_to timeouts, F request-votes and F vote responses per timeout, one
-      // leader, and the request-vote, vote-response and append-entries messages
-      const uint32_t ne = wave_sum(el ? 1u : 0u), nt = wave_sum(el_to);
-      if (lane < 6) {
-        const int idx = lane == 0 ? RAFT_CTR_EV_TIMEOUT : lane == 1 ? RAFT_CTR_EV_RV
-                      : lane == 2 ? RAFT_CTR_EV_VR : lane == 3 ? RAFT_CTR_LEADERS
-                      : lane == 4 ? RAFT_CTR_SENT : RAFT_CTR_DELIVERED;
-        const uint32_t v = lane == 0 ? nt : lane == 3 ? ne : lane <= 2 ? (uint32_t)F * nt
-                                                                   : (uint32_t)F * (2 * nt + ne);
-        atomicAdd(&ctr[idx], (unsigned long long)v);
-      }
+  // request-vote, vote-response and append-entries messages (3F; the responses are in nae).
+  if (__builtin_amdgcn_ballot_w64(el)) {                   // wave-uniform
+    // per election: el_to timeouts, F request-votes and F vote responses per timeout, one
+    // leader, and the request-vote, vote-response and append-entries messages
+    unsigned long long* const ctr = wave_counters(S, blockIdx.x * 4 + wave);
+    const uint32_t ne = wave_sum(el ? 1u : 0u), nt = wave_sum(el_to);
+    if (lane < 6) {
+      const int idx = lane == 0 ? RAFT_CTR_EV_TIMEOUT : lane == 1 ? RAFT_CTR_EV_RV
+                    : lane == 2 ? RAFT_CTR_EV_VR : lane == 3 ? RAFT_CTR_LEADERS
+                    : lane == 4 ? RAFT_CTR_SENT : RAFT_CTR_DELIVERED;
+      const uint32_t v = lane == 0 ? nt : lane == 3 ? ne : lane <= 2 ? (uint32_t)F * nt
+                                                                 : (uint32_t)F * (2 * nt + ne);
+      atomicAdd(&ctr[idx], (unsigned long long)v);
     }
   }
   // ---------------------------------------------------------------- catch-up
@@ -1802,13 +1853,8 @@ __global__ void __launch_bounds__(LANE_WG) steady_lane_kernel(DevSim S, uint32_t
     tick_wave<N, false, false, true, true>(S, t0, nt, reinterpret_cast<uint32_t*>(img), (int)lane,
                                            0, 1, blc, nbw, blt, blockIdx.x * 4 + wave);
   }
-#ifdef RS_WAVELOG   // the wave's end: its stores issued, counted, its catch-up run
-  if (lane == 0 && S.wavelog) {
-    const uint64_t wl_done = wall_clock64();
-    uint32_t* rec = S.wavelog + (size_t)(blockIdx.x * 4 + wave) * 32;
-    rec[17] = (uint32_t)wl_done;
-    rec[18] = (uint32_t)(wl_done >> 32);
-  }
+#ifdef RS_WAVELOG
+  wave_done();
 #endif
 }
 

@@ -45,6 +45,12 @@ def main(argv=None):
             print("    ..rounds done    us:", q((x3 - x2)[m] / 100.0))
             print("    ..image, rings   us:", q((a[:, 9] - x3)[m] / 100.0))
             print("    ..lines stored   us:", q((end - start - a[:, 9])[m] / 100.0))
+            if a[:, 19].any():   # the stamp before the line-store block's first image read
+                q2 = lambda x: " ".join(  # noqa: E731  (the clock's own resolution, 0.01 us)
+                    f"{v:8.2f}" for v in np.percentile(x, [0, 10, 50, 90, 99, 100]))
+                print("      body end -> store block      us:", q2((a[:, 19] - a[:, 9])[m] / 100.0))
+                print("      store block -> stores issued us:",
+                      q2((end - start - a[:, 19])[m] / 100.0))
     print("lanes on    p0/10/50/90/99/100:", q(a[:, 7]))
     print("events/lane min p0/10/50/90/99/100:", q(a[:, 10]))
     print("events/lane max p0/10/50/90/99/100:", q(a[:, 11]))
